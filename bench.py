@@ -9,15 +9,18 @@ states (per-env seed 1234+i) and U(-1,1) actions re-drawn every step, both resid
 the timed region.  N>1: env instances are sharded across ranks, no data-path collective (weak
 scaling: 1024 envs per GPU).
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3                        # the plain run: set up, warm up, time, print the line
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR     # ... and write the last timed step's outputs as DIR/<name>.npy
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full                 # ... and every further measurement (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...      # without a launcher: starts the N ranks itself (before any GPU call)
 
-The JSON line carries, besides the contract's keys: `roofline` (SURVEY.md 8(d)'s algorithmic-bytes convention, with
-the PMC-measured HBM rate beside it), `roofline_valu` (the physically binding one: fp64 VALU issue), `copy_ceiling`
-(an on-box streaming-copy rate next to the 8 TB/s spec), `cpu_baseline` and `extra` (gym-API rate, configs[4] 3D,
-fp32 variant, a 128x64 grid on the streaming 2D path -- all measured in this run).
+The JSON line carries, besides the contract's keys: `roofline` (SURVEY.md 8(d)'s algorithmic-bytes convention, from the HIP-event
+times of the timed steps themselves, with the PMC-measured HBM rate of profiles/ beside it) and `roofline_valu` (the physically
+binding one: fp64 VALU issue).  Whatever takes runs of its own is measured only with `--full`: `cpu_baseline` (null without it) and
+`extra` (the streaming-copy ceiling next to the 8 TB/s spec, gym-API rate, configs[4] 3D, fp32 variant, a 128x64 grid on the
+streaming 2D path -- all measured in that run; `--no-cpu-baseline` / `--no-extra` leave one of the two out of a `--full` run).
 """
 import argparse
 import glob
@@ -225,7 +228,27 @@ def timed_loop(torch, dev, barrier, fn, K):
     return time.perf_counter() - t0
 
 
-def run_3d(ctx, B, K, W, ra, precision="f64"):
+DUMP_SAMPLE_BYTES = 40 << 20     # the one output that can be large is cut to a sample of envs of at most this size (64 MB in all)
+
+
+def sample_envs(np, B, bytes_per_env):
+    """every env when their output fits DUMP_SAMPLE_BYTES, else a fixed (seed 0) sorted sample of envs that does"""
+    n = max(1, min(B, DUMP_SAMPLE_BYTES // bytes_per_env))
+    return np.arange(B) if n == B else np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+
+
+def dump_outputs(ctx, dst, arrays):
+    """--dump-outputs: what the timed path left for its caller after the last timed step, one DIR/<name>.npy each (float32 outputs
+    as float32, everything else as float64); with N > 1 every rank writes its shard's as <name>.rank<r>.npy"""
+    np = ctx["np"]
+    os.makedirs(dst, exist_ok=True)
+    tag = f".rank{ctx['rank']}" if ctx["world"] > 1 else ""
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        np.save(os.path.join(dst, f"{name}{tag}.npy"), a)
+
+
+def run_3d(ctx, B, K, W, ra, precision="f64", dump=None):
     """configs[4]: 3D 32x48x48, Ra=1e4, heater_duration 0.125, dt_solver 0.01 (13 RK3 substeps per env-step)."""
     torch, np, _native, sharding = ctx["torch"], ctx["np"], ctx["_native"], ctx["sharding"]
     dev, rank, world = ctx["dev"], ctx["rank"], ctx["world"]
@@ -244,6 +267,12 @@ def run_3d(ctx, B, K, W, ra, precision="f64"):
     ms = sim.profile_read(K)
     nan_envs = int(sim.get_flags().sum())
     nu = sim.get_nusselt()
+    if dump:
+        cells = 32 * 48 * 48
+        envs = sample_envs(np, B, 4 * cells * 4 + (4 * cells + 48 * 48) * 8)
+        b, u, v, w = sim.get_fields()
+        dump_outputs(ctx, dump, {"state": sim.get_state()[envs], "b": b[envs], "u": u[envs], "v": v[envs], "w": w[envs], "sample_envs": envs,
+                                 "nusselt": nu, "nan_flags": sim.get_flags()})
     rank_elapsed, rank_nan = sharding.gather_run(elapsed, nan_envs, device=ctx["red_dev"], dist=ctx["dist"] if world > 1 else None)
     elapsed, nan_total = sharding.reduce_run(elapsed, nan_envs, device=ctx["red_dev"], dist=ctx["dist"] if world > 1 else None)
     alg = sim.algorithmic_bytes_per_env_step() * B
@@ -393,8 +422,14 @@ def main():
                          "into contiguous equal parts, one Rayleigh number each (fixed dt=0.03 as in the reference)")
     ap.add_argument("--precision", default="f64", choices=("f64", "f32"),
                     help="arithmetic of the 2D kernel; f64 (the reference's) is the headline, f32 the variant of SURVEY 8(d) C2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra measurements (copy ceiling, gym-API rate, 3D, fp32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, in runs of their own: the CPU baseline before the GPU "
+                         "is touched, and after the timed steps the `extra` block (copy ceiling, gym-API rate, 3D, fp32, ...)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (observations, Nusselt numbers, NaN flags, and "
+                         "the float32 state and float64 fields of a fixed sample of envs) as DIR/<name>.npy, 64 MB at the most")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra measurements (copy ceiling, gym-API rate, 3D, fp32)")
     ap.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"),
                     help="nccl (= RCCL) on a multi-GPU node; gloo only to rehearse the N>1 flow with several ranks sharing one GPU")
     ap.add_argument("--dim", type=int, default=2, choices=(2, 3),
@@ -404,10 +439,10 @@ def main():
         raise SystemExit("--gpus must be >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # the ranks print the line; this process never touches the GPU.  The CPU baseline runs HERE, before the ranks exist
-        # (they would compete for the host cores), and travels to rank 0 through a file.
+        # the ranks print the line; this process never touches the GPU.  The CPU baseline (--full) runs HERE, before the ranks
+        # exist (they would compete for the host cores), and travels to rank 0 through a file.
         tmp = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             import tempfile
             fd, tmp = tempfile.mkstemp(prefix="rbc_cpu_baseline_", suffix=".json")
             with os.fdopen(fd, "w") as f:
@@ -424,9 +459,9 @@ def main():
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}")
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(dim=args.dim)
-    elif rank == 0 and os.environ.get("RBC_BENCH_CPU_BASELINE_FILE"):      # measured by the self-launching parent
+    elif rank == 0 and args.full and os.environ.get("RBC_BENCH_CPU_BASELINE_FILE"):      # measured by the self-launching parent
         try:
             cpu = json.load(open(os.environ["RBC_BENCH_CPU_BASELINE_FILE"]))
         except (OSError, ValueError):
@@ -458,7 +493,7 @@ def main():
                local_rank=local_rank, world=world, barrier=barrier)
     K, W = args.steps, args.warmup
     if args.dim == 3:
-        out = run_3d(ctx, args.batch or 32, K, W, args.ra, args.precision)
+        out = run_3d(ctx, args.batch or 32, K, W, args.ra, args.precision, dump=args.dump_outputs)
         if rank == 0:
             out["cpu_baseline"] = cpu
             print(json.dumps(out))
@@ -493,7 +528,13 @@ def main():
     kern_ms = sim.profile_read(K)
     flags = sim.get_flags()
     nan_envs = int(flags.sum())
-    nus, _ = sim.get_nusselt()
+    nus, nus_obs = sim.get_nusselt()
+    if args.dump_outputs:
+        envs = sample_envs(np, B, 3 * sim.nz * sim.nx * 4 + (3 * sim.nz + 1) * sim.nx * 8)
+        fb, fu, fw = sim.get_fields()
+        dump_outputs(ctx, args.dump_outputs, {"obs": sim.get_obs(3), "state": sim.get_state(3)[envs], "b": fb[envs], "u": fu[envs], "w": fw[envs],
+                                              "sample_envs": envs, "nusselt_state": nus, "nusselt_obs": nus_obs, "nan_flags": flags})
+        del fb, fu, fw
     rank_elapsed, rank_nan = sharding.gather_run(elapsed, nan_envs, device=red_dev, dist=dist if world > 1 else None)
     elapsed, nan_total = sharding.reduce_run(elapsed, nan_envs, device=red_dev, dist=dist if world > 1 else None)
     alg_bytes = sim.algorithmic_bytes_per_env_step() * B          # per launch
@@ -562,7 +603,7 @@ def main():
                          if args.ra_sweep else None),
             "mean_nusselt_state": float(np.mean(nus)),
         }
-        if world == 1 and not args.no_extra:
+        if world == 1 and args.full and not args.no_extra:
             extra = {}
             try:
                 extra["copy_ceiling"] = _native.copy_ceiling(local_rank)

@@ -13,6 +13,7 @@ Outputs: ckpt2d_ra10000.npz   - 3 episodes of train/ckpt_ra10000 (b,u,w f64)
          ckpt2d_ra100000.npz  - 1 episode of train/ckpt_ra100000
          ckpt2d_ra{30000,...,10000000}_profiles.npz - per-episode row-wise moments of the 40 episodes per chaotic Ra
                                 (`make_fixtures.py profiles` writes only these)
+         ckpt2d_ra10000_train_header.bin - the first 2048 bytes (all metadata) of train/ckpt_ra10000.h5
          ckpt2d_pins.json     - per-file known-answer table (divergence, KE, Nusselt
                                 on the full state and on the 8x48 sensor grid,
                                 horizontal-mean b profile) computed with numpy from the data.
@@ -179,10 +180,19 @@ def small_h5():
             g.create_dataset(k, data=f[k][..., :2])
 
 
+def reference_header():
+    """ckpt2d_ra10000_train_header.bin: the metadata block of train/ckpt_ra10000.h5 as the reference's writer left it (compact
+    groups with Link messages; the first dataset starts at byte 2048, b / u / w follow one another without gaps) -- what the
+    dependency-free reader has to parse of a file that is itself too large to store.  Data only."""
+    with open(f"{REF}/train/ckpt_ra10000.h5", "rb") as f, open(f"{OUT}/ckpt2d_ra10000_train_header.bin", "wb") as g:
+        g.write(f.read(2048))
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["profiles"]:
         chaotic_profiles()
     else:
         main()
         small_h5()
+        reference_header()
         chaotic_profiles()

@@ -1,4 +1,5 @@
-"""bench.py prints ONE JSON line with the driver's contract keys (metric/value/unit/..., roofline, cpu_baseline)."""
+"""bench.py prints ONE JSON line with the driver's contract keys (metric/value/unit/..., roofline, cpu_baseline).  A plain run times its
+steps and nothing else; the CPU baseline and the `extra` block are measured with --full; --dump-outputs writes the last timed step's outputs."""
 import json
 import os
 import subprocess
@@ -21,7 +22,7 @@ def _run(*args):
 
 @pytest.mark.gpu
 def test_bench_line_2d_small_batch():
-    d = _run("--steps", "2", "--warmup", "1", "--batch", "64")
+    d = _run("--steps", "2", "--warmup", "1", "--batch", "64", "--full")
     assert REQUIRED <= set(d)
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is True
     assert d["unit"] == "env-steps/s" and d["dtype"] == "f64" and d["scaling"] == "weak" and d["vs_baseline"] is None
@@ -35,6 +36,59 @@ def test_bench_line_2d_small_batch():
     # the stated core count must describe compute actually obtained: N workers deliver at least half of N single workers
     assert c["cores"] <= c["affinity"] and c["single_worker"] > 0 and c["cores_effective"] > 0.5 * c["cores"], c
     assert d["nan_envs"] == 0 and d["per_rank"]["nan_envs"] == [0]
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_only_and_dumps_the_last_step(tmp_path):
+    """Without --full the line keeps every contract key but measures nothing besides the timed steps: no CPU baseline, no `extra`.
+    --dump-outputs leaves float32 / float64 .npy files, 64 MB at the most, that hold what the last timed step computed: the same
+    seeds and actions stepped here through the C ABI (1 warm-up + 2 timed steps) end in the same arrays, bit for bit."""
+    import numpy as np
+    import torch
+    from rbc_gym import _native, sharding
+    dst = tmp_path / "out"
+    d = _run("--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64", "--dump-outputs", str(dst))
+    assert REQUIRED <= set(d) and d["cpu_baseline"] is None and "extra" not in d
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "f64" and d["nan_envs"] == 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 64 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
+    got = {f[:-4]: np.load(dst / f) for f in os.listdir(dst)}
+    assert set(got) == {"obs", "state", "b", "u", "w", "sample_envs", "nusselt_state", "nusselt_obs", "nan_flags"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert np.array_equal(got["sample_envs"], np.arange(64)) and got["obs"].shape == (64, 3, 8, 48) and got["w"].shape == (64, 65, 96)
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(4321)
+    act = (torch.rand((3, 64, 12), device=dev, generator=gen, dtype=torch.float32) * 2 - 1).contiguous()
+    torch.cuda.synchronize(dev)
+    sim = _native.NativeSim(batch=64, device=0, ra=1e4)
+    sim.reset(sharding.env_seeds(1234, 0, 64))
+    for n in range(3):
+        sim.step_dev(act.data_ptr() + n * 64 * 12 * 4)
+    sim.synchronize()
+    b, u, w = sim.get_fields()
+    nus, nuo = sim.get_nusselt()
+    want = {"obs": sim.get_obs(3), "state": sim.get_state(3), "b": b, "u": u, "w": w, "nusselt_state": nus, "nusselt_obs": nuo,
+            "nan_flags": sim.get_flags().astype(np.float64)}
+    sim.close()
+    for k, a in want.items():
+        assert got[k].dtype == (np.float32 if a.dtype == np.float32 else np.float64) and np.array_equal(got[k], a), k
+
+
+def test_dump_sample_is_fixed_and_within_budget(tmp_path):
+    """CPU: the env sample of --dump-outputs is every env when that fits, else the same sorted draw every time, and the files are
+    float32 where the output is float32 and float64 otherwise."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    per_env = 3 * 64 * 96 * 4 + (3 * 64 + 1) * 96 * 8                      # float32 state + float64 b, u, w of one default 2D env
+    assert np.array_equal(bench.sample_envs(np, 64, per_env), np.arange(64))
+    e = bench.sample_envs(np, 1024, per_env)
+    assert np.array_equal(e, bench.sample_envs(np, 1024, per_env)) and np.all(np.diff(e) > 0) and 0 <= e[0] and e[-1] < 1024
+    assert 0.9 * bench.DUMP_SAMPLE_BYTES < len(e) * per_env <= bench.DUMP_SAMPLE_BYTES
+    assert 1024 * 3 * 8 * 48 * 4 + 1024 * (8 + 8 + 8) + len(e) * (per_env + 8) <= 64 << 20      # with obs, Nusselt numbers, flags: the whole dump
+    bench.dump_outputs({"np": np, "rank": 1, "world": 2}, str(tmp_path / "o"), {"a": np.ones(3, np.float32), "f": np.arange(3, dtype=np.int32)})
+    a, f = np.load(tmp_path / "o" / "a.rank1.npy"), np.load(tmp_path / "o" / "f.rank1.npy")
+    assert a.dtype == np.float32 and f.dtype == np.float64 and np.array_equal(f, [0, 1, 2])
 
 
 @pytest.mark.gpu
@@ -72,7 +126,7 @@ def test_self_launched_two_rank_rehearsal_on_one_gpu():
     box) and rank 0 prints one n_gpus=2 line whose value counts the envs of both shards."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "2",
-                          "--warmup", "1", "--batch", "32"], capture_output=True, text=True, timeout=600, env=env)
+                          "--warmup", "1", "--batch", "32", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -96,7 +150,7 @@ def test_self_launched_four_rank_rehearsal_on_one_gpu():
     length four, the CPU baseline taken by the parent before the ranks existed."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--dist-backend", "gloo", "--steps", "3",
-                          "--warmup", "1", "--batch", "128"], capture_output=True, text=True, timeout=900, env=env)
+                          "--warmup", "1", "--batch", "128", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -111,7 +165,7 @@ def test_self_launched_four_rank_rehearsal_on_one_gpu():
 
 @pytest.mark.gpu
 def test_extra_keys_are_measured_in_the_same_run():
-    d = _run("--steps", "2", "--warmup", "1", "--batch", "64", "--no-cpu-baseline")
+    d = _run("--steps", "2", "--warmup", "1", "--batch", "64", "--full", "--no-cpu-baseline")
     x = d["extra"]
     assert "error" not in x, x
     assert x["copy_ceiling"]["kernel_gbs"] > 500 and x["copy_ceiling"]["memcpy_d2d_gbs"] > 500

@@ -59,9 +59,23 @@ def test_minimal_hdf5_reader(golden_dir, ckpt_ra1e4):
         read_checkpoint(os.path.join(golden_dir, "missing.h5"))
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/data/checkpoints"), reason="reference data only exists in the build container")
-def test_reader_on_the_reference_files(ckpt_ra1e4):
-    ck = read_checkpoint("/root/reference/data/checkpoints/train/ckpt_ra10000.h5")   # compact-group (Link message) layout
+def test_reader_on_the_reference_files(tmp_path, golden_dir, ckpt_ra1e4):
+    """The reference's own train/ckpt_ra10000.h5 (compact-group (Link message) layout, 20 episodes) is 2.9 MB, so the fixture holds
+    what the reader has to parse: the file's metadata block, its first 2048 bytes, verbatim (tests/golden/make_fixtures.py).  The
+    data region behind it is rebuilt in that file's order -- b, u, w as contiguous little-endian float64 (Nz[+1], 1, Nx, E), the
+    episode index fastest -- from the three stored episodes; with all 20 episodes this gives the reference's file byte for byte,
+    here episodes 3..19 stay zero."""
+    with open(os.path.join(golden_dir, "ckpt2d_ra10000_train_header.bin"), "rb") as f:
+        head = f.read()
+    assert len(head) == 2048
+    p = tmp_path / "ckpt_ra10000.h5"
+    with open(p, "wb") as f:
+        f.write(head)
+        for k in "buw":
+            a = np.zeros(ckpt_ra1e4[k].shape[1:] + (20,))
+            a[..., :3] = np.moveaxis(ckpt_ra1e4[k], 0, -1)
+            f.write(a.astype("<f8").tobytes())
+    ck = read_checkpoint(str(p))
     assert ck["num_episodes"] == 20 and ck["start_seed"] == 42
     for k in "buw":
         assert np.array_equal(ck[k][:3], ckpt_ra1e4[k])
