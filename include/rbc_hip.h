@@ -136,6 +136,31 @@ int   rbc_get_cell_distances(rbc_handle *h, double height, double *out);
 void *rbc_dev_cell_dist(rbc_handle *h);
 int   rbc_debug_cell_distances(int device, const float *uy, int B, int nx, double lx, double height, double *out);
 
+/* render() of the 3D env (rbc3D.py:247-318) on the device: a volume ray-caster over the temperature field of the envs
+   first_env .. first_env + n_envs - 1 of a dim=3 handle, read from the solver's own current state (float64 or float32; never the
+   float32 observation buffer, so rbc_set_obs_normalization does not change the picture).  The picture is defined in DESIGN.md
+   section 3c -- orthographic camera looking against view_from, point data on the box [0, (n-1) h] with the reference's y flip
+   (rbc3D.py:275), samples every `step` plus one partial segment, trilinear interpolation, the caller's table lut[256][4] (float32
+   RGBA in [0, 1], host pointer) read at 255 (T - clim[0]) / (clim[1] - clim[0]) with linear interpolation, segment opacity
+   1 - (1 - a)^(length / unit), front-to-back compositing over bg -- and is NOT a pixel copy of VTK's output.
+   step <= 0: half the smallest grid spacing; unit <= 0: box diagonal / (mean(nx, ny, nz) - 1).  A NaN sample is transparent.
+   out: uint8 [n_envs][height][width][3] on the host, row 0 at the top.  Runs on the handle's stream behind the last step.
+   RBC_ERR_INVALID: dim=2 handle; a null argument; width or height outside [1, 16384]; n_envs < 1, n_envs > 65535 or an env range
+   outside the batch; view_from zero or not finite; clim not finite or clim[1] == clim[0]; bg not finite; a table entry outside
+   [0, 1] (NaN included); step or unit not finite, or step shorter than box diagonal / 65536 (a ray never takes more samples than
+   that); a grid with fewer than two points along an axis.  RBC_ERR_NOT_INITIALIZED before the first reset.
+   rbc_dev_frames: the device buffer the last call filled (NULL before the first call).                                    */
+typedef struct rbc_render3_params {
+    int32_t width, height;
+    double  view_from[3];    /* direction from the scene towards the camera                  */
+    double  clim[2];
+    double  step, unit;
+    double  bg[3];
+    int32_t first_env, n_envs;
+} rbc_render3_params;
+int   rbc_render3(rbc_handle *h, const rbc_render3_params *p, const float *lut, uint8_t *out);
+void *rbc_dev_frames(rbc_handle *h);
+
 /* Page-locked host buffers for the rbc_get_* outputs: a pinned destination takes the float32 state copy of 1024 envs (75 MB)
    at PCIe speed.  Plain helpers over hipHostMalloc / hipHostFree; any rbc_get_* accepts either kind of pointer.  Into PAGEABLE
    memory, rbc_get_obs / rbc_get_state outputs of 8 MiB and more are staged in chunks through a page-locked buffer of the handle
@@ -189,9 +214,11 @@ void *rbc_dev_fields(rbc_handle *h);   /* float64 [B][ b(nz*nx) | u(nz*nx) | w((
                                           currently holds the state (it alternates between two with every RK3 stage) */
 
 /* measurement support for bench.py: HIP events are recorded on the handle's stream around
-   every step-kernel launch of rbc_step / rbc_step_dev (up to max_launches launches between
+   every step-kernel launch of rbc_step / rbc_step_dev and the kernel of rbc_render3 (up to max_launches launches between
    two reads; 0 disables).  rbc_profile_read waits for the recorded launches, writes their
-   durations in milliseconds to ms[0..capacity) and returns how many it wrote (-1 on error). */
+   durations in milliseconds to ms[0..capacity) and returns how many it wrote (-1 on error).  The durations come in issue
+   order and carry no tag: a caller that steps AND renders between two reads gets both kinds mixed -- read (or switch
+   profiling off) before rendering if only step times are wanted. */
 int    rbc_set_profiling(rbc_handle *h, int max_launches);
 int    rbc_profile_read(rbc_handle *h, double *ms, int capacity);
 /* On-box streaming ceiling to report next to the 8 TB/s spec: copies `bytes` (rounded down to 16) from one

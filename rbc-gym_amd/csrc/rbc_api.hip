@@ -6,6 +6,7 @@
 // There is deliberately no CPU fallback: every entry point that needs the GPU fails with
 // RBC_ERR_DEVICE when HIP does.
 #include "rbc2d_instances.hpp"
+#include "rbc3d_render.hpp"
 
 #include "../../include/rbc_hip.h"
 
@@ -72,6 +73,9 @@ struct rbc_handle {
     double *d_fields = nullptr, *d_ra = nullptr, *d_tri = nullptr, *d_nu = nullptr, *d_dbg = nullptr, *d_park = nullptr, *d_celld = nullptr;
     float *d_actions = nullptr, *d_obs = nullptr, *d_state = nullptr;
     uint8_t *d_mask = nullptr;
+    uint8_t *d_frames = nullptr;       // rbc_render3: frames of the last call (grown on demand), and the caller's table
+    size_t frames_cap = 0;
+    float *d_lut = nullptr;
     uint64_t *d_seeds = nullptr;
     int *d_flags = nullptr;
     unsigned long long *d_stamps = nullptr;   // RBC_STAMPS diagnostic builds only
@@ -401,7 +405,7 @@ int rbc_destroy(rbc_handle *h)
     if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
     if (h->s3) RBC_S3(h, destroy3d, h);
     void *bufs[] = {h->d_fields, h->d_ra, h->d_tri, h->d_nu, h->d_dbg, h->d_park, h->d_celld, h->d_actions, h->d_obs, h->d_state,
-                    h->d_mask, h->d_seeds, h->d_flags, h->d_stamps};
+                    h->d_mask, h->d_seeds, h->d_flags, h->d_stamps, h->d_frames, h->d_lut};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
@@ -766,6 +770,65 @@ int rbc_debug_cell_distances(int device, const float *uy, int B, int nx, double 
     if (e != hipSuccess) return fail(RBC_ERR_DEVICE, std::string("rbc_debug_cell_distances: ") + hipGetErrorString(e));
     return RBC_OK;
 }
+
+int rbc_render3(rbc_handle *h, const rbc_render3_params *p, const float *lut, uint8_t *out)
+{
+    if (int rc = check_handle(h)) return rc;
+    if (!is3d(h)) return fail(RBC_ERR_INVALID, "rbc_render3 needs a dim=3 handle (the 2D envs render their float32 state on the host)");
+    if (!p || !lut || !out) return fail(RBC_ERR_INVALID, "rbc_render3: null argument");
+    if (p->width < 1 || p->height < 1 || p->width > 16384 || p->height > 16384) return fail(RBC_ERR_INVALID, "rbc_render3: width and height must be in [1, 16384]");
+    if (p->n_envs < 1 || p->first_env < 0 || p->first_env > h->B - p->n_envs || p->n_envs > 65535)
+        return fail(RBC_ERR_INVALID, "rbc_render3: env range [first_env, first_env + n_envs) must lie inside the batch");
+    double vv = 0.0;
+    for (int k = 0; k < 3; ++k) vv += p->view_from[k] * p->view_from[k];
+    if (!(vv > 0.0) || !std::isfinite(vv)) return fail(RBC_ERR_INVALID, "rbc_render3: view_from must be a finite non-zero vector");
+    if (!std::isfinite(p->clim[0]) || !std::isfinite(p->clim[1]) || p->clim[0] == p->clim[1]) return fail(RBC_ERR_INVALID, "rbc_render3: clim must be finite with cmax != cmin");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(p->bg[k])) return fail(RBC_ERR_INVALID, "rbc_render3: bg must be finite");
+    for (int q = 0; q < 1024; ++q)
+        if (!(lut[q] >= 0.0f && lut[q] <= 1.0f)) return fail(RBC_ERR_INVALID, "rbc_render3: table entries must be in [0, 1]");
+    const rbc_config &c = h->cfg;
+    if (c.nx < 2 || c.ny < 2 || c.nz < 2) return fail(RBC_ERR_INVALID, "rbc_render3: needs at least two lattice points per axis");
+    rbcr::RenderSetup rs{};
+    rs.nx = c.nx; rs.ny = c.ny; rs.nz = c.nz;
+    rs.lx = c.lx; rs.ly = c.ly; rs.lz = c.lz;
+    rs.width = p->width; rs.height = p->height; rs.n_envs = p->n_envs;
+    const double hx = c.lx / c.nx, hy = c.ly / c.ny, hz = c.lz / c.nz;
+    const double diag = std::sqrt((c.nx - 1) * hx * (c.nx - 1) * hx + (c.ny - 1) * hy * (c.ny - 1) * hy + (c.nz - 1) * hz * (c.nz - 1) * hz);
+    rs.step = p->step > 0.0 ? p->step : 0.5 * std::fmin(hx, std::fmin(hy, hz));
+    rs.unit = p->unit > 0.0 ? p->unit : diag / ((c.nx + c.ny + c.nz) / 3.0 - 1.0);
+    if (!std::isfinite(rs.step) || !std::isfinite(rs.unit) || !(diag / rs.step <= 65536.0))
+        return fail(RBC_ERR_INVALID, "rbc_render3: step and unit must be finite, and step no shorter than box diagonal / 65536");
+    for (int k = 0; k < 3; ++k) { rs.view_from[k] = p->view_from[k]; rs.bg[k] = p->bg[k]; }
+    rs.clim[0] = p->clim[0]; rs.clim[1] = p->clim[1];
+    if (int rc = all_initialized(h)) return rc;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    const size_t bytes = (size_t)p->n_envs * p->height * p->width * 3;
+    if (h->frames_cap < bytes) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (h->d_frames) { (void)hipFree(h->d_frames); h->d_frames = nullptr; h->frames_cap = 0; }
+        HIP_TRY(hipMalloc(&h->d_frames, bytes));
+        h->frames_cap = bytes;
+    }
+    if (!h->d_lut) HIP_TRY(hipMalloc(&h->d_lut, 1024 * sizeof(float)));
+    HIP_TRY(hipMemcpyAsync(h->d_lut, lut, 1024 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    // the buffer that holds the current state alternates with the RK3 stages: taken the way rbc_get_fields3 / rbc_dev_fields take it
+    rs.env_stride = RBC_S3(h, env_stride3d, h);
+    const size_t esz = h->s3_f32 ? sizeof(float) : sizeof(double);
+    const char *state = static_cast<const char *>(RBC_S3(h, dev_fields3d, h)) + (size_t)p->first_env * rs.env_stride * esz;
+    const bool rec = h->profiling && 2 * (h->ev_used + 1) <= h->ev.size();
+    if (rec) HIP_TRY(hipEventRecord(h->ev[2 * h->ev_used], h->stream));
+    HIP_TRY(rbcr::launch_render3(rs, state, h->s3_f32, h->d_lut, h->d_frames, h->stream));
+    if (rec) {
+        HIP_TRY(hipEventRecord(h->ev[2 * h->ev_used + 1], h->stream));
+        h->ev_used++;
+    }
+    HIP_TRY(hipMemcpyAsync(out, h->d_frames, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return RBC_OK;
+}
+
+void *rbc_dev_frames(rbc_handle *h) { return h ? h->d_frames : nullptr; }
 
 void *rbc_host_alloc(size_t bytes)
 {

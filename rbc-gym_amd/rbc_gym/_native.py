@@ -32,6 +32,11 @@ class RbcConfig(C.Structure):
                 ("batch", C.c_int32), ("device", C.c_int32), ("write_state", C.c_int32), ("precision", C.c_int32),
                 ("reference_clock", C.c_int32)]
 
+class RbcRender3Params(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("view_from", C.c_double * 3), ("clim", C.c_double * 2),
+                ("step", C.c_double), ("unit", C.c_double), ("bg", C.c_double * 3), ("first_env", C.c_int32), ("n_envs", C.c_int32)]
+
+
 PRECISIONS = {"f64": 0, "f32": 1}
 # rbc_config.reference_clock (include/rbc_hip.h): "documented" = every env-step integrates heater_duration, what the reference's
 # sources say (rbc_sim2D_api.jl:84-85); "recorded" = what its recorded flowstats series show: the first env-step after a reset
@@ -94,6 +99,8 @@ SYMBOLS = {
     "rbc_reset_from_arrays3": (C.c_int, [_vp, _u8p, _dp, _dp, _dp, _dp]),
     "rbc_get_fields3": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     "rbc_debug_tendencies3": (C.c_int, [_vp, _fp, _dp, _dp, _dp, _dp]),
+    "rbc_render3": (C.c_int, [_vp, C.POINTER(RbcRender3Params), _fp, _u8p]),
+    "rbc_dev_frames": (_vp, [_vp]),
 }
 
 _lib = None
@@ -532,6 +539,31 @@ class NativeSim3D:
 
     get_obs = get_state          # rbc3D.py:229-232: the observation is the full state
 
+    def render(self, size=(800, 608), view_from=(1.0, 1.0, 1.0), clim=None, lut=None, step=0.0, unit=0.0, bg=(1.0, 1.0, 1.0),
+               first_env=0, n_envs=None):
+        """uint8 (n_envs, height, width, 3): the temperature field of the envs first_env ... through the device's volume ray-caster
+        (include/rbc_hip.h rbc_render3; the picture is defined in DESIGN.md section 3c and is not a pixel copy of VTK's).
+        size = (width, height); clim defaults to the plate temperatures (rbc3D.py:278-279); lut: float32 (256, 4) RGBA in [0, 1],
+        default envs._common.volume_lut(); step / unit <= 0: the library's defaults.  The default unit, box diagonal /
+        (mean(nx, ny, nz) - 1), is what PyVista's add_volume is recalled to use -- PyVista is not installed here: unchecked."""
+        if lut is None:
+            from .envs._common import volume_lut
+            lut = volume_lut()
+        lut = np.ascontiguousarray(lut, dtype=np.float32)
+        if lut.shape != (256, 4):
+            raise ValueError(f"render: lut must have shape (256, 4), got {lut.shape}")
+        n = self.B - int(first_env) if n_envs is None else int(n_envs)
+        p = RbcRender3Params()
+        p.width, p.height = int(size[0]), int(size[1])
+        p.view_from[:] = [float(x) for x in view_from]
+        p.clim[:] = [self.cfg.min_b, self.cfg.min_b + self.cfg.delta_b] if clim is None else [float(x) for x in clim]
+        p.step, p.unit = float(step), float(unit)
+        p.bg[:] = [float(x) for x in bg]
+        p.first_env, p.n_envs = int(first_env), n
+        out = np.empty((max(n, 0), max(p.height, 0), max(p.width, 0), 3), np.uint8)
+        self._check(self.lib.rbc_render3(self.h, C.byref(p), _ptr(lut, _fp), _ptr(out, _u8p)))
+        return out
+
     def get_fields(self):
         s = (self.B, self.nz, self.ny, self.nx)
         b, u, v, w = np.empty(s), np.empty(s), np.empty(s), np.empty((self.B, self.nz + 1, self.ny, self.nx))
@@ -586,4 +618,4 @@ class NativeSim3D:
     def dev_ptrs(self):
         L = self.lib
         return dict(state=L.rbc_dev_state(self.h), nusselt=L.rbc_dev_nusselt(self.h), flags=L.rbc_dev_flags(self.h),
-                    fields=L.rbc_dev_fields(self.h))
+                    fields=L.rbc_dev_fields(self.h), frames=L.rbc_dev_frames(self.h))

@@ -71,6 +71,17 @@ def temperature_image(field, vmin, vmax):
     return matplotlib.colormaps["turbo"](scaled, bytes=True)[:, :, :3]
 
 
+def volume_lut():
+    """Default transfer function of the 3D render(): float32 (256, 4) RGBA.  RGB is matplotlib's turbo at 256 entries (cmap="turbo",
+    rbc3D.py:301); alpha is 1 / (1 + exp(-x)) for x = linspace(-1, 1, 256), which is PyVista's opacity="sigmoid_1" (rbc3D.py:303)
+    as recalled -- PyVista is not installed here, so that is unchecked."""
+    import matplotlib
+    lut = np.empty((256, 4), np.float32)
+    lut[:, :3] = matplotlib.colormaps["turbo"](np.linspace(0.0, 1.0, 256))[:, :3]
+    lut[:, 3] = 1.0 / (1.0 + np.exp(-np.linspace(-1.0, 1.0, 256)))
+    return lut
+
+
 class _Window:
     """pygame window of the 'human' render mode (rbc2D.py:222-255); created lazily, closed with the env."""
 

@@ -3,7 +3,7 @@
 Drop-in for the reference class (src/rbc_gym/envs/rbc3D.py:37-339): constructor kwargs, attributes, spaces,
 reset/step conventions and info keys {t, step, nusselt}; its Julia calls (rbc3D.py:175,206,230,235,239-240,328-329)
 become calls on a dim=3 handle of librbc_hip.so.  The observation is the full float32 state (4, Nz, Ny, Nx).
-PyVista volume rendering (display only) is not reproduced.
+render() (rbc3D.py:247-318) is a volume ray-caster on the device.
 """
 from typing import Optional
 
@@ -11,7 +11,7 @@ import numpy as np
 
 from .._gym import gym
 from .. import _native
-from ._common import NativeEnvBase, box_stack, env_logger
+from ._common import NativeEnvBase, _Window, box_stack, env_logger
 
 INF = float("inf")
 
@@ -48,8 +48,12 @@ class RayleighBenardConvection3DEnv(NativeEnvBase):
         device: int = 0,
         precision: str = "f64",          # "f64": the reference's Float64 arithmetic; "f32": the float32 instantiation of the 3D kernels
         reference_clock: str = "documented",   # "recorded": the solver-step count of the reference's recorded series
+        render_size: tuple = (800, 608),       # (width, height) of a frame: the reference's window_size (rbc3D.py:297)
+        view_from: tuple = (1, 1, 1),          # direction from the scene towards the camera; (1, 1, 1) is PyVista's isometric view
     ) -> None:
         super().__init__()
+        self.render_size, self.view_from = tuple(int(n) for n in render_size), tuple(float(x) for x in view_from)
+        self._window = _Window(self.render_size, self.metadata["render_fps"])
         self.precision = precision
         self.reference_clock = reference_clock
         self.ra, self.pr = rayleigh_number, prandtl_number
@@ -83,6 +87,17 @@ class RayleighBenardConvection3DEnv(NativeEnvBase):
         return {"t": float(t), "step": int(step), "nusselt": float(self.sim.get_nusselt()[0])}
 
     def render(self):
-        if self.render_mode is None:
+        """The temperature field through the device's volume ray-caster (NativeSim3D.render): "rgb_array" returns the (height, width,
+        3) uint8 frame, (608, 800, 3) like the reference's screenshot; "human" shows it in a window.  Orthographic camera, the
+        reference's colour map, clim and y flip (rbc3D.py:275-303) -- no axes widget, no perspective, no shading, none of VTK's
+        jittering: not a pixel copy of the reference's picture.  The default opacity table and opacity unit distance are PyVista's as
+        recalled, unchecked (see NativeSim3D.render, _common.volume_lut)."""
+        if self.render_mode is None:                              # rbc3D.py:260-265
             return None
-        raise NotImplementedError("PyVista volume rendering of the reference (display only) is not part of this build")
+        frame = self.sim.render(size=self.render_size, view_from=self.view_from, clim=self.temperature_difference)[0]
+        if self.render_mode == "rgb_array":
+            return frame
+        if self.render_mode == "human":
+            self._window.show(frame.transpose(1, 0, 2), self.render_size)
+            return None
+        raise ValueError(f"Unknown render mode: {self.render_mode}")

@@ -98,8 +98,8 @@ def make_sb3_vec_env(env_id, n_envs, normalize=None, **env_kwargs):
             return [False for _ in self._idx(indices)]
 
         def get_images(self):
-            # the 3D batched env has no render() (PyVista display only in the reference) and render_mode may be None
-            if not callable(getattr(self.batched, "render", None)) or getattr(self.batched, "render_mode", None) is None:
+            # render_mode may be None (both batched envs render: the 3D one through the device's ray-caster)
+            if getattr(self.batched, "render_mode", None) is None:
                 return [None] * self.num_envs
             frames = self.batched.render()
             return list(frames) if frames is not None else [None] * self.num_envs

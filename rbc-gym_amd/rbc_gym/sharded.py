@@ -141,6 +141,11 @@ class ShardedSim:
     def get_cell_distances(self, *a):
         return self._cat(self._all(lambda r, sim: sim.get_cell_distances(*a)))
 
+    def render(self, **kw):
+        if "first_env" in kw or "n_envs" in kw:              # per-handle arguments: a global env range is not mapped onto the shards
+            raise ValueError("a sharded sim renders all its envs: first_env / n_envs are not supported")
+        return self._cat(self._all(lambda r, sim: sim.render(**kw)))
+
     def synchronize(self):
         self._all(lambda r, sim: sim.synchronize())
 

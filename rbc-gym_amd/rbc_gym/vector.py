@@ -224,13 +224,14 @@ class RayleighBenardConvection2DVectorEnv(_BatchedEnv):
 class RayleighBenardConvection3DVectorEnv(_BatchedEnv):
     """Batched 3D env (BASELINE.json configs[4]: 32 envs per GPU): constructor kwargs of the reference's 3D env
     (rbc3D.py:43-61) plus num_envs / device; observations are the float32 states (B, 4, Nz, Ny, Nx), info {t, step, nusselt}."""
-    metadata = {"render_modes": [], "autoreset_mode": "NextStep"}
+    metadata = {"render_modes": ["rgb_array"], "render_fps": 10, "autoreset_mode": "NextStep"}
     _fields = ("b", "u", "v", "w")
 
     def __init__(self, num_envs=1, rayleigh_number=2500, prandtl_number=0.7, domain=(2, 4 * np.pi, 4 * np.pi),
                  state_shape=(16, 32, 32), temperature_difference=(1, 2), heater_segments=8, heater_limit=0.9,
                  heater_duration=0.125, episode_length=300, dt_solver=0.01, use_gpu=True, checkpoint=None, checkpoint_idx=None,
-                 render_mode=None, device=0, devices=None, precision="f64", obs_buffers=None, reference_clock="documented", **_ignored):
+                 render_mode=None, device=0, devices=None, precision="f64", obs_buffers=None, reference_clock="documented",
+                 render_size=(800, 608), view_from=(1, 1, 1), **_ignored):
         # obs_buffers: None = every reset / step returns a new observation array as far as the caller can tell (the reference's
         # behaviour; large ones come from _native.PinnedPool: a page-locked array is reused only once the caller has dropped it),
         # "fresh" = always np.empty (the A/B partner), "pinned" = the observations rotate over three page-locked buffers
@@ -238,6 +239,7 @@ class RayleighBenardConvection3DVectorEnv(_BatchedEnv):
         # either way: 5.7k instead of 3.6k env-steps/s through the gym API
         from .envs.rbc3D import build_spaces3d
         self.obs_buffers = obs_buffers
+        self.render_size, self.view_from = tuple(int(n) for n in render_size), tuple(float(x) for x in view_from)
         self._pinned, self._pin_at = None, 0
         self.num_envs = int(num_envs)
         self.reference_clock = reference_clock                       # "recorded": see _native.CLOCKS
@@ -285,6 +287,17 @@ class RayleighBenardConvection3DVectorEnv(_BatchedEnv):
             return views(self.sim.dev_ptrs(), self.num_envs)
         return [dict(views(p, count), device=dev, env_range=(start, start + count))
                 for p, dev, (start, count) in zip(self.sim.dev_ptrs(), self.devices, self.sim.ranges)]
+
+    def render(self):
+        """The frames of all envs as one (num_envs, height, width, 3) uint8 array, frame i what the single env's render() returns
+        for env i (envs/rbc3D.py): one launch of the device's volume ray-caster over the batch."""
+        if self.render_mode is None:
+            gym.logger.warn("You are calling render method without specifying any render mode. "
+                            "You can specify the render_mode at initialization, ")
+            return None
+        if self.render_mode != "rgb_array":
+            raise ValueError(f"the batched env renders rgb_array frames only, not {self.render_mode!r}")
+        return self.sim.render(size=self.render_size, view_from=self.view_from, clim=self.temperature_difference)
 
     def _stacked_info(self):
         t, step = self.sim.get_info()
