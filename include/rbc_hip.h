@@ -52,7 +52,11 @@ typedef struct rbc_config {
                                 actions, dt_* in free-fall units scaled by t_ff = lz^2, 4 channels b,u,v,w) */
     int32_t nx, ny, nz;      /* grid = state_shape[::-1]  (96, 1, 64).  dim=2, float64: any nx, nz >= 8 (the reference
                                 takes any grid: rbc_sim2D_api.jl:17-25); the LDS-resident kernel where it is built for
-                                the grid, the streaming kernels with ny = 1 otherwise          */
+                                the grid, the streaming kernels with ny = 1 otherwise.
+                                dim=3: every direction >= 8.  Horizontal slabs that fit one workgroup's LDS (nx*ny <=
+                                ~5000 in float64, ~10000 in float32) take the slab projection, larger ones the row /
+                                pencil projection, whose bound is one (y, z) plane in LDS:
+                                ny*nz <= ~5000 (float64), ~10000 (float32); beyond it rbc_create returns RBC_ERR_INVALID */
     double  lx, ly, lz;      /* L = [2*pi, 2]                                   (api:28)     */
     double  ra;              /* default Rayleigh number for every env            (api:17)     */
     double  pr;              /* 0.7                                             (api:35)     */

@@ -35,6 +35,9 @@ struct rbc3_state {
     int fuse2d = 0;                    // streaming-2D: N1 of the one-kernel projection (k2s_project_fused), 0 = the separate kernels
     size_t fuse2d_lds = 0;
     int fft_threads = 256;             // slab-FFT workgroup: one round of work items for the larger of nx, ny (8 items per line)
+    int pencil = 0;                    // 3D: rows of y per workgroup of the row / pencil projection (k3p_*), 0 = the slab kernels
+    size_t pencil_x_lds = 0, pencil_yz_lds = 0;
+    real *tab_pencil = nullptr;        // the pivot table in the order [m][k][ky], m = 0 .. nx/2 (k3p_yz_solve reads a plane of it contiguously)
     int march = 0;                     // 3D: 2 = k3_ifft_march (inverse FFT + the whole correction), 0 = k3_ifft_pair + k3_correct_w
     double tff = 1.0;
     // Le-Moin RK3 ([OC] TimeSteppers/runge_kutta_3.jl).  Builds made with -DRBC_EXPERIMENTS=1 (never the shipped library) read
@@ -233,6 +236,24 @@ int create3d(rbc_handle *h)
 #undef RBC_IP_ATTR
         }
     }
+    // 3D grids whose slab does not fit the slab-FFT workgroup take the row / pencil projection (RBC_3D_PENCIL=1 forces it on any 3D
+    // grid, the A/B partner of the slab kernels); its own bound is the (env, m) plane of k3p_yz_solve: two copies of nz lines of ny | 1
+    // complex values plus the y twiddles.  Rows per workgroup of the two x kernels: 32, fewer where the rows are long.
+    const char *pe = std::getenv("RBC_3D_PENCIL");
+    if (!h->stream2d && (s->fft_lds > (size_t)RBC_LDS_CEILING || (pe && pe[0] == '1'))) {
+        s->pencil_yz_lds = ((size_t)2 * c.nz * K3::slab_row(ny) + ny) * sizeof(real2);
+        if (s->pencil_yz_lds > (size_t)RBC_LDS_CEILING)
+            return fail(RBC_ERR_INVALID, std::string("3D grid too large for the pencil projection: one (y, z) plane must fit the LDS, ny*nz <= ~") +
+                                         (std::is_same<real, double>::value ? "5000 (float64)" : "10000 (float32)"));
+        int R = 32;
+        auto x_lds = [&](int r) { return ((size_t)(r + 2) * K3::slab_row(c.nx) + c.nx) * sizeof(real2); };      // k3p_ifftx_correct's, the larger of the two
+        while (R > 2 && x_lds(R) > 64 * 1024) R /= 2;
+        if (x_lds(R) > (size_t)RBC_LDS_CEILING) return fail(RBC_ERR_INVALID, "3D grid too large for the pencil projection: a row pair of this nx does not fit the LDS (nx <= ~3400)");
+        s->pencil = R; s->pencil_x_lds = x_lds(R);
+        RBC_LDS_ATTR(K3::k3p_div_fftx);
+        RBC_LDS_ATTR(K3::k3p_yz_solve);
+        RBC_LDS_ATTR(K3::k3p_ifftx_correct);
+    } else
     if (s->fft_lds > 160 * 1024) return fail(RBC_ERR_INVALID, "3D horizontal slab too large for the LDS FFT (nx*ny <= ~5000)");
     const size_t B = h->B;
     for (int q = 0; q < 2; ++q) {
@@ -275,6 +296,15 @@ int create3d(rbc_handle *h)
             std::vector<real> tr(tab.begin(), tab.end());          // pivots are computed in float64, stored in the solver's precision
             HIP3(hipMalloc(&s->tab, tr.size() * sizeof(real)));
             HIP3(hipMemcpy(s->tab, tr.data(), tr.size() * sizeof(real), hipMemcpyHostToDevice));
+        }
+        if (s->pencil) {
+            const int nm = c.nx / 2 + 1;
+            std::vector<real> tp((size_t)nm * c.nz * ny);
+            for (int m = 0; m < nm; ++m)
+                for (int k = 0; k < c.nz; ++k)
+                    for (int n = 0; n < ny; ++n) tp[((size_t)m * c.nz + k) * ny + n] = (real)tab[((size_t)k * ny + n) * c.nx + m];
+            HIP3(hipMalloc(&s->tab_pencil, tp.size() * sizeof(real)));
+            HIP3(hipMemcpy(s->tab_pencil, tp.data(), tp.size() * sizeof(real), hipMemcpyHostToDevice));
         }
         if (s->ip2d) {                   // position p = 8 k1 + k2 holds mode m = k1 + N1 k2 (rowfft_inplace)
             const int N1 = s->ip2d, nx = c.nx;
@@ -328,7 +358,7 @@ int create3d(rbc_handle *h)
     // float32: 9.36k -> 9.10k (-2.8 %), with the prefetch 9.37k -> 9.31k (-0.6 %): keeps k3_ifft_pair + k3_correct_w.  float64 planes
     // beyond 6 columns per thread (64 x 64) keep the separate pass too (the prefetch does not fit 256 registers).
     // RBC_IFFT_MARCH=0 | 2 overrides (0: the A/B partner, bitwise the same state; also what the streaming-2D grids run).
-    if (!h->stream2d && c.nz % 4 == 0 && !h->no_pair && (size_t)c.nx * ny <= (size_t)(std::is_same<real, double>::value ? 6 : 8) * s->fft_threads) {
+    if (!s->pencil && !h->stream2d && c.nz % 4 == 0 && !h->no_pair && (size_t)c.nx * ny <= (size_t)(std::is_same<real, double>::value ? 6 : 8) * s->fft_threads) {
         int m = std::is_same<real, double>::value ? 2 : 0;
         if (const char *e = std::getenv("RBC_IFFT_MARCH")) m = std::atoi(e);
         s->march = (m == 2) ? 2 : 0;
@@ -370,7 +400,7 @@ void destroy3d(rbc_handle *h)
     for (hipStream_t q : s->gstream) if (q) { (void)hipStreamSynchronize(q); (void)hipStreamDestroy(q); }
     for (hipEvent_t e : s->gdone) if (e) (void)hipEventDestroy(e);
     if (s->gstart) (void)hipEventDestroy(s->gstart);
-    void *bufs[] = {s->st[0], s->st[1], s->lead_save, s->gm, s->phy, s->phy2, s->tab_perm, s->partner, s->phi, s->spec, s->jct, s->tw, s->actT, s->tab, s->dbg, s->out_part, s->out_arrive};
+    void *bufs[] = {s->st[0], s->st[1], s->lead_save, s->gm, s->phy, s->phy2, s->tab_perm, s->tab_pencil, s->partner, s->phi, s->spec, s->jct, s->tw, s->actT, s->tab, s->dbg, s->out_part, s->out_arrive};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     delete s;
@@ -392,6 +422,16 @@ int project3d(rbc_handle *h, const rbc3_grp &q, int which, double dts, const uin
     real *buf = s->st[which] + (size_t)q.e0 * g.env_stride;
     real *phi = s->phi + (size_t)q.e0 * g.nc;
     const uint8_t *mk = mask ? mask + q.e0 : nullptr;
+    if (s->pencil) {                         // rows along x -> (env, m) planes: y transform, z solve, inverse y transform -> rows along x
+        real2 *spec = s->spec + (size_t)q.e0 * (g.nx / 2 + 1) * g.ny * g.nz;
+        const dim3 gx((unsigned)((size_t)B * g.nz * ((g.ny + s->pencil - 1) / s->pencil)));
+        hipLaunchKernelGGL(K3::k3p_div_fftx, gx, dim3(256), s->pencil_x_lds, q.st, g, s->plan, buf, spec, dts, s->pencil);
+        hipLaunchKernelGGL(K3::k3p_yz_solve, dim3((unsigned)(B * (g.nx / 2 + 1))), dim3(256), s->pencil_yz_lds, q.st, g, s->plan, spec, s->tab_pencil);
+        hipLaunchKernelGGL(K3::k3p_ifftx_correct, gx, dim3(256), s->pencil_x_lds, q.st, g, s->plan, spec, phi, buf, dts, mk, s->pencil);
+        hipLaunchKernelGGL(K3::k3_correct_w, grid_for((size_t)B * (g.nc - pln), 256), dim3(256), 0, q.st, g, buf, phi, dts, B, mk);
+        HIP3(hipGetLastError());
+        return RBC_OK;
+    }
     if (s->fuse2d && g.nz % 2 == 0 && !h->no_pair) {
         const int fthr = 512;             // measured: 256 -> 512 threads +12 % (more loads in flight around the LDS phases); 768 / 1024: no better
 #define RBC_FUSE_LAUNCH(N1_) if (s->fuse2d == N1_) hipLaunchKernelGGL(K3::k2s_project_fused<N1_>, dim3(B), dim3(fthr), s->fuse2d_lds, q.st, g, s->plan, buf, phi, s->tab, dts, mk, want_phi ? 1 : 0);

@@ -8,6 +8,8 @@
 //   cell-per-thread kernels as fallbacks for other grid shapes) -> k3_rhs_fft_pair (divergence of two mirror
 //   slabs as one complex 2D FFT in LDS) -> k3_thomas_pair_fused (z solve per (kx,ky) from both walls on the
 //   packed spectrum) -> k3_ifft_pair (inverse FFT + u, v correction) -> k3_correct_w.
+// Grids whose horizontal slab does not fit one workgroup's LDS project by rows and pencils instead: k3p_div_fftx -> k3p_yz_solve ->
+// k3p_ifftx_correct -> k3_correct_w.
 // The batch is cut into env groups whose chains run on separate streams (one captured graph per env-step).
 // Same discretisation as the 2D kernel; layouts [k][j][i].
 // The second half of the file is the streaming-2D mode: 2D grids without an LDS-resident kernel on these

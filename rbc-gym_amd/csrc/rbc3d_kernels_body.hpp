@@ -1508,6 +1508,171 @@ __global__ void k3_correct(Geo3 g, real *st, const real *phi, real dts, int B, c
     if (k > 0) sb[3 * (size_t)g.nc + c0] -= (pc - p[c0 - pln]) * g.rdz * dts;
 }
 
+// ---- row / pencil projection (3D grids whose horizontal slab does not fit one workgroup's LDS) ------------------------------------
+// No kernel below holds a whole (x, y) slab.  k3p_div_fftx transforms rows along x, two real rows packed as one complex row, and
+// unpacks them to the half spectrum m = 0 .. nx/2 in the PENCIL layout spec[env][m][k][j] (j contiguous); k3p_yz_solve owns one
+// (env, m) plane of that layout: y transform of its nz lines, the real tridiagonal z solve of every (m, ky) column on the real and
+// the imaginary part alike, inverse y transform, all in LDS; k3p_ifftx_correct rebuilds the Hermitian halves of its rows, transforms
+// back and corrects u and v.  The mirror-slab packing is not used: it couples mode (mx, ky) to (-mx, -ky), another workgroup's here.
+// The kernels are compiled without packed float32 instructions (device pass only, like the ray-caster); slab_fft / slab_dft are
+// inlined at the call so that their arithmetic is compiled under the same setting.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define RBC_PENCIL_TARGET __attribute__((target("no-packed-fp32-ops")))
+#else
+#define RBC_PENCIL_TARGET
+#endif
+
+__device__ __forceinline__ RBC_PENCIL_TARGET void pencil_barrier()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// transform of `lines` lines of n = n1 * n2 values (element stride 1, line stride ls) held in S; D: a second buffer of the same
+// size.  Returns where the result is (D after the register-blocked transform, S after the generic one).
+__device__ __forceinline__ RBC_PENCIL_TARGET real2 *pencil_lines(real2 *S, real2 *D, int lines, int n, int n1, int n2, int ls,
+                                                                 const real2 *tw, int sign)
+{
+#define RBC_LINES(N1_) if (n2 == 8 && n1 == N1_) { [[clang::always_inline]] slab_fft<N1_>(S, D, lines, ls, 1, tw, sign); return D; }
+    RBC_LINES(4) RBC_LINES(6) RBC_LINES(8) RBC_LINES(12) RBC_LINES(16)      // (DFT-24 / -32 in registers: the generic routine instead)
+#undef RBC_LINES
+    [[clang::always_inline]] slab_dft(S, S, lines, n, n1, n2, ls, 1, tw, sign, D);
+    return S;
+}
+
+// divergence of cell (i, j) of level k (u, v, w: that level's planes), the expression of k3_rhs_fft; 0 for the row past the last one
+// (the partner of an unpaired last row)
+__device__ __forceinline__ RBC_PENCIL_TARGET real pencil_div(const Geo3 &g, const real *u, const real *v, const real *w, int k, int j, int i)
+{
+    const int nx = g.nx, ny = g.ny, pln = nx * ny;
+    if (j >= ny) return real(0.0);
+    const int ip = (i + 1 == nx) ? 0 : i + 1, jp = (j + 1 == ny) ? 0 : j + 1, c = j * nx + i;
+    const real wt = (k + 1 < g.nz) ? w[pln + c] : real(0.0);
+    const real wb = (k > 0) ? w[c] : real(0.0);
+    return (u[j * nx + ip] - u[c]) * g.rdx + (v[jp * nx + i] - v[c]) * g.rdy + (wt - wb) * g.rdz;
+}
+
+// Kernel A: divergence of U*/dts of RY rows of one level -> x spectrum, half of it, in the pencil layout.
+// grid = B * nz * ceil(ny / RY) workgroups, RY even; LDS: 2 * (RY/2) * slab_row(nx) + nx complex values.
+__global__ RBC_PENCIL_TARGET void __launch_bounds__(256) k3p_div_fftx(Geo3 g, FftPlan pl, const real *st, real2 *spec, real dts, int RY)
+{
+    extern __shared__ __attribute__((aligned(16))) real2 sm[];
+    const int nx = g.nx, ny = g.ny, nz = g.nz, pln = nx * ny, nm = nx / 2 + 1, nby = (ny + RY - 1) / RY;
+    const int env = blockIdx.x / (nz * nby), rest = blockIdx.x - env * (nz * nby), k = rest / nby, j0 = (rest - k * nby) * RY;
+    const int rows = (ny - j0 < RY) ? ny - j0 : RY, lines = (rows + 1) / 2;
+    const int nxp = slab_row(nx);
+    real2 *S = sm, *D = sm + (RY / 2) * nxp, *twx = sm + RY * nxp;
+    for (int t = threadIdx.x; t < nx; t += blockDim.x) twx[t] = pl.tw[t];
+    const real *sb = st + (size_t)env * g.env_stride;
+    const real *u = sb + g.nc + (size_t)k * pln, *v = sb + 2 * (size_t)g.nc + (size_t)k * pln, *w = sb + 3 * (size_t)g.nc + (size_t)k * pln;
+    const real rdt = real(1.0) / dts;
+    for (int idx = threadIdx.x; idx < lines * nx; idx += blockDim.x) {
+        const int l = idx / nx, i = idx - l * nx;
+        S[l * nxp + i] = make_real2(pencil_div(g, u, v, w, k, j0 + 2 * l, i) * rdt, pencil_div(g, u, v, w, k, j0 + 2 * l + 1, i) * rdt);
+    }
+    pencil_barrier();
+    const real2 *Z = pencil_lines(S, D, lines, nx, pl.nx1, pl.nx2, nxp, twx, -1);
+    // rows a (real part) and b (imaginary part) of a line: A[m] = (Z[m] + conj Z[nx-m]) / 2, B[m] = (Z[m] - conj Z[nx-m]) / 2i
+    real2 *o = spec + (((size_t)env * nm) * nz + k) * ny + j0;
+    for (int idx = threadIdx.x; idx < nm * rows; idx += blockDim.x) {
+        const int m = idx / rows, r = idx - m * rows;
+        const real2 p = Z[(r >> 1) * nxp + m], q = Z[(r >> 1) * nxp + ((m == 0) ? 0 : nx - m)];
+        o[(size_t)m * nz * ny + r] = (r & 1) ? make_real2(real(0.5) * (p.y + q.y), real(0.5) * (q.x - p.x))
+                                             : make_real2(real(0.5) * (p.x + q.x), real(0.5) * (p.y - q.y));
+    }
+}
+
+// Kernel B: one (env, m) plane of the pencil layout, nz lines of ny values, never leaves LDS between the y transform, the z solve
+// and the inverse y transform.  The z solve is k3_thomas's recurrence (pivots 1/piv_k with the pinned mean mode in the table) with
+// one thread per (ky, real | imaginary part): consecutive threads touch consecutive reals of a level.  tabp: the pivots in the
+// order [m][k][ky], fetched BK levels ahead of the recurrence.  grid = B * (nx/2 + 1); LDS: 2 * nz * (ny|1) + ny complex values.
+__global__ RBC_PENCIL_TARGET void __launch_bounds__(256) k3p_yz_solve(Geo3 g, FftPlan pl, real2 *spec, const real *tabp)
+{
+    extern __shared__ __attribute__((aligned(16))) real2 sm[];
+    const int nx = g.nx, ny = g.ny, nz = g.nz, nm = nx / 2 + 1, nyp = slab_row(ny);
+    const int env = blockIdx.x / nm, m = blockIdx.x - env * nm;
+    real2 *S = sm, *D = sm + nz * nyp, *twy = sm + 2 * nz * nyp;
+    for (int t = threadIdx.x; t < ny; t += blockDim.x) twy[t] = pl.tw[nx + t];
+    real2 *io = spec + ((size_t)env * nm + m) * nz * ny;
+    for (int idx = threadIdx.x; idx < nz * ny; idx += blockDim.x) { const int k = idx / ny; S[idx + k * (nyp - ny)] = io[idx]; }
+    pencil_barrier();
+    real2 *P = pencil_lines(S, D, nz, ny, pl.ny1, pl.ny2, nyp, twy, -1);
+    {
+        const real *tm = tabp + (size_t)m * nz * ny;
+        const real o = g.rdz * g.rdz;
+        constexpr int BK = 8;
+        for (int t = threadIdx.x; t < 2 * ny; t += blockDim.x) {
+            const int ky = t >> 1;
+            real *col = reinterpret_cast<real *>(P) + t;           // real (t even) or imaginary (t odd) part of column ky, level stride 2 nyp
+            real y = real(0.0);
+            int k = 0;
+            for (; k + BK <= nz; k += BK) {
+                real inv[BK];
+#pragma unroll
+                for (int q = 0; q < BK; ++q) inv[q] = tm[(k + q) * ny + ky];
+#pragma unroll
+                for (int q = 0; q < BK; ++q) { y = col[2 * (k + q) * nyp] * inv[q] - (inv[q] * o) * y; col[2 * (k + q) * nyp] = y; }
+            }
+            for (; k < nz; ++k) { const real inv = tm[k * ny + ky]; y = col[2 * k * nyp] * inv - (inv * o) * y; col[2 * k * nyp] = y; }
+            real x = real(0.0);
+            k = nz - 1;
+            for (; k - BK + 1 >= 0; k -= BK) {
+                real cp[BK];
+#pragma unroll
+                for (int q = 0; q < BK; ++q) cp[q] = tm[(k - q) * ny + ky] * o;
+#pragma unroll
+                for (int q = 0; q < BK; ++q) { x = col[2 * (k - q) * nyp] - cp[q] * x; col[2 * (k - q) * nyp] = x; }
+            }
+            for (; k >= 0; --k) { const real cp = tm[k * ny + ky] * o; x = col[2 * k * nyp] - cp * x; col[2 * k * nyp] = x; }
+        }
+    }
+    pencil_barrier();
+    const real2 *Q = pencil_lines(P, P == S ? D : S, nz, ny, pl.ny1, pl.ny2, nyp, twy, +1);
+    for (int idx = threadIdx.x; idx < nz * ny; idx += blockDim.x) { const int k = idx / ny; io[idx] = Q[idx + k * (nyp - ny)]; }
+}
+
+// Kernel C: RY rows of one level plus the row below them (the halo d(phi)/dy needs): Hermitian halves rebuilt from m = 0 .. nx/2,
+// two real rows per complex line, inverse x transform, phi = result / (nx ny); then u -= dts d(phi)/dx, v -= dts d(phi)/dy with the
+// operand order of k3_correct, and phi of the RY rows to the phi buffer (k3_correct_w reads it).  A masked env is left alone.
+// grid = B * nz * ceil(ny / RY); LDS: 2 * (RY/2 + 1) * slab_row(nx) + nx complex values.
+__global__ RBC_PENCIL_TARGET void __launch_bounds__(256) k3p_ifftx_correct(Geo3 g, FftPlan pl, const real2 *spec, real *phi, real *st, real dts,
+                                                                           const uint8_t *mask, int RY)
+{
+    extern __shared__ __attribute__((aligned(16))) real2 sm[];
+    const int nx = g.nx, ny = g.ny, nz = g.nz, pln = nx * ny, nm = nx / 2 + 1, nby = (ny + RY - 1) / RY;
+    const int env = blockIdx.x / (nz * nby), rest = blockIdx.x - env * (nz * nby), k = rest / nby, j0 = (rest - k * nby) * RY;
+    if (mask && !mask[env]) return;                               // masked reset: this env is not being projected
+    const int rows = (ny - j0 < RY) ? ny - j0 : RY, R = rows + 1, lines = (R + 1) / 2;      // local row 0 = the halo j0 - 1, local row r = j0 + r - 1
+    const int nxp = slab_row(nx), jh = (j0 == 0) ? ny - 1 : j0 - 1;
+    real2 *S = sm, *D = sm + (RY / 2 + 1) * nxp, *twx = sm + (RY + 2) * nxp;
+    for (int t = threadIdx.x; t < nx; t += blockDim.x) twx[t] = pl.tw[t];
+    // Z = A + i B on every line (A, B: spectra of its two real rows): Z[m] = A[m] + i B[m], Z[nx-m] = conj A[m] + i conj B[m]
+    const real2 *in = spec + (((size_t)env * nm) * nz + k) * ny;
+    for (int idx = threadIdx.x; idx < nm * lines; idx += blockDim.x) {
+        const int m = idx / lines, l = idx - m * lines, ra = 2 * l, rb = 2 * l + 1;
+        const real2 *im_ = in + (size_t)m * nz * ny;
+        const real2 a = im_[(ra == 0) ? jh : j0 + ra - 1];
+        const real2 b = (rb < R) ? im_[j0 + rb - 1] : make_real2(real(0.0), real(0.0));
+        S[l * nxp + m] = make_real2(a.x - b.y, a.y + b.x);
+        if (m != 0 && nx - m != m) S[l * nxp + nx - m] = make_real2(a.x + b.y, b.x - a.y);
+    }
+    pencil_barrier();
+    const real2 *P = pencil_lines(S, D, lines, nx, pl.nx1, pl.nx2, nxp, twx, +1);
+    const real *Pr = reinterpret_cast<const real *>(P);           // local row r, column i: Pr[2 ((r >> 1) nxp + i) + (r & 1)]
+    const real sc = real(1.0) / ((real)nx * (real)ny);
+    real *sb = st + (size_t)env * g.env_stride;
+    real *u = sb + g.nc + (size_t)k * pln, *v = sb + 2 * (size_t)g.nc + (size_t)k * pln, *po = phi + ((size_t)env * nz + k) * pln;
+    for (int idx = threadIdx.x; idx < rows * nx; idx += blockDim.x) {
+        const int r = idx / nx + 1, i = idx - (r - 1) * nx, iw = (i == 0) ? nx - 1 : i - 1, c = (j0 + r - 1) * nx + i;
+        const real pc = Pr[2 * ((r >> 1) * nxp + i) + (r & 1)] * sc, pw = Pr[2 * ((r >> 1) * nxp + iw) + (r & 1)] * sc;
+        const real ps = Pr[2 * (((r - 1) >> 1) * nxp + i) + ((r - 1) & 1)] * sc;
+        po[c] = pc;
+        u[c] -= (pc - pw) * g.rdx * dts;
+        v[c] -= (pc - ps) * g.rdy * dts;
+    }
+}
+
 // copy b (unchanged by a projection-only pass) between state buffers
 __global__ void k3_copy(real *dst, const real *src, size_t n)
 {
