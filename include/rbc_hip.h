@@ -56,7 +56,10 @@ typedef struct rbc_config {
                                 dim=3: every direction >= 8.  Horizontal slabs that fit one workgroup's LDS (nx*ny <=
                                 ~5000 in float64, ~10000 in float32) take the slab projection, larger ones the row /
                                 pencil projection, whose bound is one (y, z) plane in LDS:
-                                ny*nz <= ~5000 (float64), ~10000 (float32); beyond it rbc_create returns RBC_ERR_INVALID */
+                                ny*nz <= ~5000 (float64), ~10000 (float32); beyond it rbc_create returns RBC_ERR_INVALID.
+                                Tendencies: LDS tiles over full rows of x up to nx = 64, x- and y-tiled LDS tiles on wider grids
+                                with nx % 32 == 0, ny % 8 == 0, nz % 4 == 0, the z-marching kernels otherwise
+                                (rbc_debug_tendency_path tells which)                                                          */
     double  lx, ly, lz;      /* L = [2*pi, 2]                                   (api:28)     */
     double  ra;              /* default Rayleigh number for every env            (api:17)     */
     double  pr;              /* 0.7                                             (api:35)     */
@@ -242,6 +245,12 @@ int  rbc_debug_substeps(rbc_handle *h, const float *actions, int nsub, double dt
    1 if every group replays its own captured graph on a stream with a hardware queue of its own (found by probing at rbc_create), 0 if
    the groups are branches of one graph (or launches are direct).  A handle on the LDS-resident 2D kernel reports {1, 0}.          */
 int  rbc_debug_launch_plan(rbc_handle *h, int groups[2]);
+/* which tendency kernels the handle's stage plan launches (what the step selects, not a re-derivation): *path = 0 cell-per-thread,
+   1 z-marching, 2 LDS tiles over full rows of x, 3 flat tiles (streaming 2D), 4 x- and y-tiled LDS tiles (grids wider than 64 cells);
+   -1 for a handle on the LDS-resident 2D kernel.  Environment, read when a step is issued: RBC_NO_TILE=1 no tile kernel at all,
+   RBC_TILE_SHAPE=16x16|16x8|16x4|8x8 forces a full-row shape, RBC_TILE_X=0 keeps wide grids on the z-marching kernels, RBC_TILE_X=1
+   takes the x-tiled kernel on every 3D grid with nx % 32 == 0, ny % 8 == 0, nz % 4 == 0 (nx <= 64 included).                      */
+int  rbc_debug_tendency_path(rbc_handle *h, int *path);
 /* diagnostic builds only (-DRBC_STAMPS=1): per-phase shader-clock cycles of the last launch,
    out[B][64]; returns RBC_ERR_INVALID in the shipped build                                 */
 int  rbc_debug_stamps(rbc_handle *h, unsigned long long *out);

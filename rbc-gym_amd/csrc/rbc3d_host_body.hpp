@@ -106,6 +106,10 @@ constexpr int RBC_LDS_CEILING = 160 * 1024;
 #endif
 constexpr int TW3 = std::is_same<real, float>::value ? RBC_F32_TILE_WAVES : 3;
 
+// waves per SIMD the 256-thread x-tiled kernels (32 x 8 columns) are compiled for: float64 needs 170 VGPRs -- two over the cap of three
+// waves, which spilled -- so two (two workgroups per CU, the waves of one 32 x 16 workgroup); float32 fits three
+constexpr int TWX8 = std::is_same<real, float>::value ? 3 : 2;
+
 inline rbc3_state *S3(const rbc_handle *h) { return static_cast<rbc3_state *>(h->s3); }
 
 // true if a kernel on `b` can run while one is running on `a`, i.e. the two streams do not share a hardware queue: `a` is held
@@ -538,6 +542,75 @@ void wall3d(rbc_handle *h, const rbc3_grp &q, const float *actions_dev, int zero
                            s->actT + (size_t)q.e0 * g.heaters * g.heaters, zero);
 }
 
+// Which tendency kernels a stage launches for a group of nominal size Bn: 0 = none of the tile kernels (z-marching or cell-per-thread
+// fallback), 1 .. 4 full-row tiles, 5 .. 9 FLAT tiles (streaming 2D), 10 .. 15 x-tiled (10 + 3 * (TY == 8) + {16: 0, 8: 1, 4: 2}[KT]).
+// advance3d launches by it and rbc_debug_tendency_path reports it: one function, so the query cannot drift from the launch.
+int tend_shape3d(const rbc_handle *h, int Bn)
+{
+    const K3::Geo3 &g = S3(h)->g;
+    auto tiles_fit = [&](int ty, int kt, int maxt) {
+        const int thr = g.nx * ty;
+        return !h->no_tile && g.nz % kt == 0 && g.ny % ty == 0 && thr <= maxt && thr % 64 == 0 && g.nx <= K3::NXP3 &&
+               (ty + 6) * g.nx <= 2 * thr;
+    };
+    // LDS-tiled tendency kernels (planes staged once per level; first half of the grid: (u, v), second half: (w, b)).  Tile shapes
+    // (rows of y x levels of z): tall tiles win (fewer chunk prologues: the z windows of a column are loaded once per chunk) as
+    // long as the launch still has about a hundred workgroups (a group of 8 configs[4] envs: 96); small batches take
+    // 16 x 4.  RBC_TILE_SHAPE=16x16|16x8|16x4|8x8 forces one (A/B runs).
+    const char *tshape = std::getenv("RBC_TILE_SHAPE");
+    auto want = [&](const char *name, bool dflt) { return tshape ? std::strcmp(tshape, name) == 0 : dflt; };
+    int shape = 0;
+    auto wgs = [&](int ty, int kt) { return 2 * Bn * (g.ny / ty) * (g.nz / kt); };      // workgroups of one (full-sized) group's launch
+    // float32: the tall tiles only once a launch has ~two hundred workgroups.  With four chains in flight a 96-workgroup launch per chain
+    // is 384 workgroups on 256 CUs -- a round and a half -- and the half-empty second round costs the float32 kernel (shorter levels,
+    // more issue-bound) more than the extra chunk prologues of 16 x 8 tiles: configs[4] float32 9.37k -> 9.94k env-steps/s (+6 %;
+    // float64 prefers the tall tiles: 6.66k against 6.40k).  B = 64: 16 x 16 again (192 workgroups per launch), 10.8k.
+    const int tall_min = std::is_same<real, float>::value ? 192 : 96;
+    if (want("16x16", wgs(16, 16) >= tall_min) && tiles_fit(16, 16, 768)) shape = 1;
+    else if (want("16x8", wgs(16, 8) >= 96) && tiles_fit(16, 8, 768)) shape = 2;
+    else if (want("16x4", true) && tiles_fit(16, 4, 768)) shape = 3;
+    else if (want("8x8", true) && tiles_fit(8, 8, 512)) shape = 4;
+    // Grids wider than a full-row tile: x- and y-tiled (k3_tilex_all), 32 columns x 16 rows, or x 8 where ny % 16 != 0, marching 16 / 8 / 4
+    // levels by the same thresholds on the workgroup count -- of ONE env's launch (an x tile multiplies the count by nx / 32: wide grids
+    // have the workgroups at any batch size), so the height depends on the grid alone.  With a height that followed the batch size, a batch
+    // of 9 and a batch of 1 differed at round-off (tests/test_gpu_pencil3d.py compares them bit for bit; the face flux at a chunk's bottom
+    // comes from the prologue's copy of the expression, every other one from the level loop's -- the likely cause, not isolated).
+    // RBC_TILE_X=0 keeps the z-marching fallback (the A/B partner), RBC_TILE_X=1 takes this kernel on every 3D grid that meets its
+    // divisibility conditions, before the full-row shapes.
+    const char *tx = std::getenv("RBC_TILE_X");
+    const bool tx_off = tx && tx[0] == '0', tx_force = tx && tx[0] == '1';
+    if (!h->stream2d && !h->no_tile && !tx_off && (tx_force || (!shape && g.nx > K3::NXP3)) && g.nx % 32 == 0 && g.ny % 8 == 0 && g.nz % 4 == 0) {
+        const int ty = (g.ny % 16 == 0) ? 16 : 8;
+        auto wgx = [&](int kt) { return 2 * (g.nx / 32) * (g.ny / ty) * (g.nz / kt); };
+        const int kt = (g.nz % 16 == 0 && wgx(16) >= tall_min) ? 16 : ((g.nz % 8 == 0 && wgx(8) >= 96) ? 8 : 4);
+        shape = 10 + (ty == 8 ? 3 : 0) + (kt == 16 ? 0 : (kt == 8 ? 1 : 2));
+    }
+    // streaming-2D mode: the same bodies with one-row planes (FLAT), a workgroup = one row of nx threads marching 16 / 8 / 4 levels
+    // (tall chunks while the launch keeps a few hundred workgroups; a small batch takes 4 levels: its step is a chain of short kernels)
+    if (h->stream2d && !h->no_tile && g.nx <= 256 && g.nz % 4 == 0) {
+        auto enough = [&](int kt) { return g.nz % kt == 0 && 2 * (size_t)Bn * (g.nz / kt) >= 256; };
+        shape = (g.nz >= 64 && enough(32)) ? 8 : (enough(16) ? 5 : (enough(8) ? 6 : 7));     // 32 levels: +1.8 % at 128 x 64 (64: -6 %)
+        if (const char *e = std::getenv("RBC_FLAT_KT")) {                                      // A/B knob: 4, 8, 16, 32, 64
+            const int kt = std::atoi(e);
+            if (kt > 0 && g.nz % kt == 0) shape = kt == 64 ? 9 : (kt == 32 ? 8 : (kt == 16 ? 5 : (kt == 8 ? 6 : (kt == 4 ? 7 : shape))));
+        }
+    }
+    return shape;
+}
+
+// rbc_debug_tendency_path: 0 cell-per-thread, 1 z-marching, 2 full-row tiles, 3 flat (streaming 2D), 4 x-tiled
+int tendency_path3d(const rbc_handle *h)
+{
+    const rbc3_state *s = S3(h);
+    const int per_slice = (h->B + s->slices - 1) / s->slices;
+    const int Bn = s->groups <= 1 ? per_slice : (per_slice + s->groups - 1) / s->groups;      // the nominal group size run_step3d hands to advance3d
+    const int shape = tend_shape3d(h, Bn);
+    if (shape >= 10) return 4;
+    if (shape >= 5) return 3;
+    if (shape >= 1) return 2;
+    return (s->g.nz % K3::KC3 == 0 && !h->no_march) ? 1 : 0;
+}
+
 // the stage list of `nsub` substeps (the last of size dt_last) for one group of envs, starting from state buffer `which`;
 // actions already on the device.  Returns the buffer that holds the state afterwards through *which_out.
 // (st0, st1: the range of RK3 stages, counted 0 .. 3 nsub - 1 over the whole interval, this call issues -- `which` is the buffer the
@@ -556,40 +629,8 @@ int advance3d(rbc_handle *h, const rbc3_grp &q, int which, const float *actions_
     real *gm = s->gm + eo, *phy = s->phy + (size_t)q.e0 * g.nc;
     const double *actT = s->actT + (size_t)q.e0 * (g.wall_nx ? (size_t)g.wall_nx : (size_t)g.heaters * g.heaters);
     const double *ra = h->d_ra + (size_t)q.e0 * 2;
-    auto tiles_fit = [&](int ty, int kt, int maxt) {
-        const int thr = g.nx * ty;
-        return !h->no_tile && g.nz % kt == 0 && g.ny % ty == 0 && thr <= maxt && thr % 64 == 0 && g.nx <= K3::NXP3 &&
-               (ty + 6) * g.nx <= 2 * thr;
-    };
-    // LDS-tiled tendency kernels (planes staged once per level; first half of the grid: (u, v), second half: (w, b)).  Tile shapes
-    // (rows of y x levels of z): tall tiles win (fewer chunk prologues: the z windows of a column are loaded once per chunk) as
-    // long as the launch still has about a hundred workgroups (a group of 8 configs[4] envs: 96); small batches take
-    // 16 x 4.  RBC_TILE_SHAPE=16x16|16x8|16x4|8x8 forces one (A/B runs).
-    const char *tshape = std::getenv("RBC_TILE_SHAPE");
-    auto want = [&](const char *name, bool dflt) { return tshape ? std::strcmp(tshape, name) == 0 : dflt; };
+    const int shape = tend_shape3d(h, q.nominal());
     const bool no_nxc = [] { const char *e = std::getenv("RBC_NO_CONST_GRID"); return e && e[0] == '1'; }();      // A/B: the generic instantiations
-    int shape = 0;
-    const int Bn = q.nominal();
-    auto wgs = [&](int ty, int kt) { return 2 * Bn * (g.ny / ty) * (g.nz / kt); };      // workgroups of one (full-sized) group's launch
-    // float32: the tall tiles only once a launch has ~two hundred workgroups.  With four chains in flight a 96-workgroup launch per chain
-    // is 384 workgroups on 256 CUs -- a round and a half -- and the half-empty second round costs the float32 kernel (shorter levels,
-    // more issue-bound) more than the extra chunk prologues of 16 x 8 tiles: configs[4] float32 9.37k -> 9.94k env-steps/s (+6 %;
-    // float64 prefers the tall tiles: 6.66k against 6.40k).  B = 64: 16 x 16 again (192 workgroups per launch), 10.8k.
-    const int tall_min = std::is_same<real, float>::value ? 192 : 96;
-    if (want("16x16", wgs(16, 16) >= tall_min) && tiles_fit(16, 16, 768)) shape = 1;
-    else if (want("16x8", wgs(16, 8) >= 96) && tiles_fit(16, 8, 768)) shape = 2;
-    else if (want("16x4", true) && tiles_fit(16, 4, 768)) shape = 3;
-    else if (want("8x8", true) && tiles_fit(8, 8, 512)) shape = 4;
-    // streaming-2D mode: the same bodies with one-row planes (FLAT), a workgroup = one row of nx threads marching 16 / 8 / 4 levels
-    // (tall chunks while the launch keeps a few hundred workgroups; a small batch takes 4 levels: its step is a chain of short kernels)
-    if (h->stream2d && !h->no_tile && g.nx <= 256 && g.nz % 4 == 0) {
-        auto enough = [&](int kt) { return g.nz % kt == 0 && 2 * (size_t)Bn * (g.nz / kt) >= 256; };
-        shape = (g.nz >= 64 && enough(32)) ? 8 : (enough(16) ? 5 : (enough(8) ? 6 : 7));     // 32 levels: +1.8 % at 128 x 64 (64: -6 %)
-        if (const char *e = std::getenv("RBC_FLAT_KT")) {                                      // A/B knob: 4, 8, 16, 32, 64
-            const int kt = std::atoi(e);
-            if (kt > 0 && g.nz % kt == 0) shape = kt == 64 ? 9 : (kt == 32 ? 8 : (kt == 16 ? 5 : (kt == 8 ? 6 : (kt == 4 ? 7 : shape))));
-        }
-    }
     for (int n = st0 / 3; n < nsub && 3 * n < st1; ++n) {
         const double d = (n == nsub - 1) ? dt_last : dt;
         for (int ph = (n == st0 / 3) ? st0 % 3 : 0; ph < 3 && 3 * n + ph < st1; ++ph) {
@@ -646,6 +687,18 @@ int advance3d(rbc_handle *h, const rbc3_grp &q, int which, const float *actions_
             else if (shape == 8) RBC_FLAT_LAUNCH(32)
             else if (shape == 9) RBC_FLAT_LAUNCH(64)
 #undef RBC_FLAT_LAUNCH
+            // x- and y-tiled: 32 x TY columns per workgroup marching KT levels (a kernel argument: one instantiation per TY)
+#define RBC_TILEX_LAUNCH(TY, KT, WAVES)                                                                                                  \
+            {                                                                                                                            \
+                constexpr size_t lds = K3::tilex_lds_bytes<32, TY>();                                                                    \
+                static_assert(lds <= 64 * 1024, "k3_tilex_all: three planes fit the LDS a launch may ask for without an attribute");     \
+                if (g.nx % 32 || g.ny % TY || g.nz % (KT) || (KT) > 16) return fail(RBC_ERR_INVALID, "k3_tilex_all: grid is not a multiple of the tile"); \
+                const dim3 gt((unsigned)(2 * (size_t)B * (g.nx / 32) * (g.ny / TY) * (g.nz / (KT)))), bt(32 * TY);                        \
+                hipLaunchKernelGGL((K3::k3_tilex_all<32, TY, 16, WAVES>), gt, bt, lds, q.st, g, cur, nxt, gm, actT, ra, d, gam[ph], zet[ph], store_g, (KT), RBC_TILE_STAMPS); \
+            }
+            else if (shape >= 10 && shape <= 12) RBC_TILEX_LAUNCH(16, 16 >> (shape - 10), 2)
+            else if (shape >= 13 && shape <= 15) RBC_TILEX_LAUNCH(8, 16 >> (shape - 13), TWX8)
+#undef RBC_TILEX_LAUNCH
             else if (g.nz % K3::KC3 == 0 && !h->no_march) {      // z-marching kernels (register reuse along z)
                 const dim3 gm_(grid_for((size_t)B * g.nx * g.ny * (g.nz / K3::KC3), 128));
                 hipLaunchKernelGGL(K3::k3_tend_march<0>, gm_, bc, 0, q.st, g, cur, nxt, gm, phy, actT, ra, d, gam[ph], zet[ph], B);

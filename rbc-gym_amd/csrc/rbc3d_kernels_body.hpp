@@ -502,9 +502,10 @@ struct TileGeo {
     static constexpr int ROWS3 = FLAT ? 1 : TY3 + 6;
     static constexpr int PLANE3 = ROWS3 * NXP;
     static constexpr int NXPAD = NXP;
-    static constexpr bool IS_FLAT = FLAT;
+    static constexpr bool IS_FLAT = FLAT, X_TILED = false;
+    static constexpr int kt = KT3;                                // levels a workgroup marches
     int nx, ny, nz, pl, rows, plane, tiles, chunks, env, j0, k0, i, jl, j, tid, nthreads;
-    __device__ __forceinline__ TileGeo(const Geo3 &g, int blk)
+    __device__ __forceinline__ TileGeo(const Geo3 &g, int blk, int)
     {
         nx = NXC ? NXC : g.nx; ny = NYC ? NYC : g.ny; nz = g.nz; pl = nx * ny; rows = ROWS3; plane = rows * nx;
         tiles = ny / TY3; chunks = nz / KT3;
@@ -520,6 +521,40 @@ struct TileGeo {
         int jy = j0 - 3 + r; jy += (jy < 0) ? ny : 0; jy -= (jy >= ny) ? ny : 0;
         return jy * nx + c;
     }
+};
+
+// x- and y-tiled geometry (k3_tilex_all, grids wider than NXP3): a workgroup owns TX3 x TY3 columns, thread = column, and a plane
+// is a full rectangle of (TY3 + 6) rows x (TX3 + 6) columns at row stride STR -- halo of 3 on every side, corners included (the
+// sym4 of the advecting component reads offsets (-2 .. +1, +1)).  The periodic wrap in x AND y is applied once, in src(), when
+// a plane is staged; every stencil read of the level loop is then `own LDS address + immediate` (the bodies' xb[] is ONE address
+// plus constants, where the full-row tiles carry seven wrapped x indices).  TX3 is a power of two: tid -> (il, jl) are a
+// mask and a shift, idx -> (row, column) of the staging a multiplication by the constant TX3 + 6.
+template <int TX3, int TY3, int KT3, int STR>
+struct TileGeoX {
+    static constexpr int ROWS3 = TY3 + 6, COLS3 = TX3 + 6;
+    static constexpr int PLANE3 = ROWS3 * STR;                    // LDS elements of a plane
+    static constexpr int NXPAD = STR;
+    static constexpr bool IS_FLAT = false, X_TILED = true;
+    static_assert((TX3 & (TX3 - 1)) == 0 && STR >= COLS3, "x tile: power of two, row stride covers the halo");
+    static constexpr int plane = ROWS3 * COLS3, nthreads = TX3 * TY3;      // elements staged per plane; workgroup size
+    int nx, ny, nz, pl, env, i0, j0, k0, i, il, jl, j, tid, kt;
+    __device__ __forceinline__ TileGeoX(const Geo3 &g, int blk, int levels)
+    {
+        nx = g.nx; ny = g.ny; nz = g.nz; pl = nx * ny;
+        kt = min(levels, KT3);                                    // the level loop stays bounded by the template constant
+        const int xtiles = nx / TX3, ytiles = ny / TY3, chunks = nz / kt;
+        const int zc = blk % chunks, r1 = blk / chunks, xt = r1 % xtiles, r2 = r1 / xtiles, yt = r2 % ytiles;
+        env = r2 / ytiles; i0 = xt * TX3; j0 = yt * TY3; k0 = zc * kt;
+        tid = threadIdx.x; jl = tid / TX3; il = tid & (TX3 - 1); i = i0 + il; j = j0 + jl;
+    }
+    __device__ __forceinline__ int src(int idx) const
+    {
+        const int r = idx / COLS3, c = idx - r * COLS3;
+        int jy = j0 - 3 + r; jy += (jy < 0) ? ny : 0; jy -= (jy >= ny) ? ny : 0;      // ny >= TY3 >= 8, nx >= TX3 >= 32: one wrap
+        int ix = i0 - 3 + c; ix += (ix < 0) ? nx : 0; ix -= (ix >= nx) ? nx : 0;
+        return jy * nx + ix;
+    }
+    __device__ __forceinline__ int dst(int idx) const { const int r = idx / COLS3, c = idx - r * COLS3; return r * STR + c; }
 };
 
 template <int NPF, class TG, class MEM>
@@ -538,7 +573,8 @@ __device__ __forceinline__ void tile_store(const TG &t, real *dst, const real (&
     for (int q = 0; q < NPF; ++q) {
         const int idx = t.tid + q * t.nthreads;
         if (idx < t.plane) {
-            if (TG::IS_FLAT) dst[idx] = pf[q];
+            if constexpr (TG::X_TILED) dst[t.dst(idx)] = pf[q];
+            else if (TG::IS_FLAT) dst[idx] = pf[q];
             else { const int r = idx / t.nx, c = idx - r * t.nx; dst[r * TG::NXPAD + c] = pf[q]; }
         }
     }
@@ -547,14 +583,17 @@ __device__ __forceinline__ void tile_store(const TG &t, real *dst, const real (&
 // (u, v): blockDim = nx * TY3, B * (ny/TY3) * (nz/KT3) workgroups, LDS = 3 planes.  Two shapes are built:
 // 16 rows x 4 levels (768 threads = 12 waves, three per SIMD, register budget 168) where ny % 16 == 0, else 8 x 8
 // (up to 512 threads, budget 256); the first is 3 % faster at 48 x 48 x 32 (smaller halo share, even SIMD load).
-template <int TY3, int KT3, int NPF, int NXP = NXP3, bool FLAT = false, int NXC = 0, int NYC = 0>
+// TG: the tile geometry -- TileGeo (full rows of x; FLAT: streaming 2D) or TileGeoX (x- and y-tiled); the arithmetic below is the same
+// for all of them, only where a plane element comes from and where a thread's stencil reads point differ.
+template <class TG, int NPF>
 __device__ __forceinline__ void tile_uv_body(const Geo3 &g, const real *cur, real *nxt, real *gm,
                                              const f64 *nu_kappa, real dt, real gam, real zet, int store_g, int blk,
-                                             const real *stamps = nullptr)
+                                             int levels, const real *stamps = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) real tile_sm[];
-    const TileGeo<TY3, KT3, NXP, FLAT, NXC, NYC> t(g, blk);
-    constexpr int PLANE3 = TileGeo<TY3, KT3, NXP, FLAT, NXC, NYC>::PLANE3;
+    const TG t(g, blk, levels);
+    constexpr int PLANE3 = TG::PLANE3, NXP = TG::NXPAD;
+    constexpr bool FLAT = TG::IS_FLAT;
     const int nx = t.nx, nz = t.nz, pl = t.pl;
     real *PU = tile_sm, *PV = tile_sm + PLANE3, *PW = tile_sm + 2 * PLANE3;        // u(k), v(k), w(k+1)
     constexpr int IU = 0, IV = PLANE3, IW = 2 * PLANE3;
@@ -563,10 +602,13 @@ __device__ __forceinline__ void tile_uv_body(const Geo3 &g, const real *cur, rea
     const size_t u = g.nc, v = 2 * (size_t)g.nc, w = 3 * (size_t)g.nc;      // element offsets of the fields inside an env's block
     const real nu = nu_kappa[2 * t.env];
     const real rdx = g.rdx, rdy = g.rdy, rdz = g.rdz, dz = g.dz, hz = dz / 2;
-    int xi[7];
-    wrap7(t.i, nx, xi);
+    int xi[7];                                                    // x- and y-tiled: the halo is in the plane, x offsets are constants
+    if constexpr (TG::X_TILED) {
+#pragma unroll
+        for (int a = 0; a < 7; ++a) xi[a] = t.il + a;
+    } else wrap7(t.i, nx, xi);
     const int col = t.j * nx + t.i;                               // own column inside a level
-    // one LDS address per x offset; the plane and the y offset are immediates of the ds_read
+    // one LDS address per x offset (TileGeoX: one address in all); the plane and the y offset are immediates of the ds_read
     const real *xb[7];
 #pragma unroll
     for (int a = 0; a < 7; ++a) xb[a] = tile_sm + (FLAT ? 0 : (t.jl + 3) * NXP) + xi[a];
@@ -612,8 +654,8 @@ __device__ __forceinline__ void tile_uv_body(const Geo3 &g, const real *cur, rea
     __syncthreads();
 
     TSTAMP_INIT;
-    for (int k = t.k0; k < t.k0 + KT3; ++k) {
-        const bool more = (k + 1 < t.k0 + KT3);
+    for (int k = t.k0; k < t.k0 + t.kt; ++k) {
+        const bool more = (k + 1 < t.k0 + t.kt);
         TSTAMP(6);
 #pragma unroll
         for (int q = 0; q < 5; ++q) { winu[q] = winu[q + 1]; winv[q] = winv[q + 1]; }
@@ -722,14 +764,15 @@ __device__ __forceinline__ void tile_uv_body(const Geo3 &g, const real *cur, rea
 }
 
 // (w, b): same shape, LDS = 2 planes (w and b at the current level)
-template <int TY3, int KT3, int NPF, int NXP = NXP3, bool FLAT = false, int NXC = 0, int NYC = 0>
+template <class TG, int NPF>
 __device__ __forceinline__ void tile_wb_body(const Geo3 &g, const real *cur, real *nxt, real *gm, const f64 *actT,
                                              const f64 *nu_kappa, real dt, real gam, real zet, int store_g, int blk,
-                                             const real *stamps = nullptr)
+                                             int levels, const real *stamps = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) real tile_sm[];
-    const TileGeo<TY3, KT3, NXP, FLAT, NXC, NYC> t(g, blk);
-    constexpr int PLANE3 = TileGeo<TY3, KT3, NXP, FLAT, NXC, NYC>::PLANE3;
+    const TG t(g, blk, levels);
+    constexpr int PLANE3 = TG::PLANE3, NXP = TG::NXPAD;
+    constexpr bool FLAT = TG::IS_FLAT;
     const int nx = t.nx, nz = t.nz, pl = t.pl;
     real *PW = tile_sm, *PB = tile_sm + PLANE3;
     constexpr int IW = 0, IB = PLANE3;
@@ -738,10 +781,15 @@ __device__ __forceinline__ void tile_wb_body(const Geo3 &g, const real *cur, rea
     const size_t b = 0, u = g.nc, v = 2 * (size_t)g.nc, w = 3 * (size_t)g.nc;      // element offsets of the fields inside an env's block
     const real nu = nu_kappa[2 * t.env], ka = nu_kappa[2 * t.env + 1];
     const real rdx = g.rdx, rdy = g.rdy, rdz = g.rdz, dz = g.dz, hz = dz / 2;
-    int xi[7];
-    wrap7(t.i, nx, xi);
+    int xi[7];                                                    // x- and y-tiled: the halo is in the plane, x offsets are constants
+    if constexpr (TG::X_TILED) {
+#pragma unroll
+        for (int a = 0; a < 7; ++a) xi[a] = t.il + a;
+    } else wrap7(t.i, nx, xi);
     const int col = t.j * nx + t.i;
-    const int colE = t.j * nx + xi[4];                            // column (i+1, j)
+    int iE = xi[4];                                               // x index of column (i+1, j)
+    if constexpr (TG::X_TILED) iE = (t.i + 1 == nx) ? 0 : t.i + 1;
+    const int colE = t.j * nx + iE;
     const int colN = ((t.j + 1 == t.ny) ? 0 : t.j + 1) * nx + t.i;   // column (i, j+1)
     const real *xb[7];
 #pragma unroll
@@ -779,8 +827,8 @@ __device__ __forceinline__ void tile_wb_body(const Geo3 &g, const real *cur, rea
     __syncthreads();
 
     TSTAMP_INIT;
-    for (int k = t.k0; k < t.k0 + KT3; ++k) {
-        const bool more = (k + 1 < t.k0 + KT3);
+    for (int k = t.k0; k < t.k0 + t.kt; ++k) {
+        const bool more = (k + 1 < t.k0 + t.kt);
         TSTAMP(6);
 #pragma unroll
         for (int q = 0; q < 5; ++q) { winw[q] = winw[q + 1]; winb[q] = winb[q + 1]; }
@@ -878,7 +926,7 @@ __device__ __forceinline__ void tile_wb_body(const Geo3 &g, const real *cur, rea
         }
     }
     TSTAMP_FLUSH(1, stamps);
-    if (t.k0 + KT3 == nz) N.st(w + (size_t)nz * pl, colb, real(0.0));      // top wall face
+    if (t.k0 + t.kt == nz) N.st(w + (size_t)nz * pl, colb, real(0.0));      // top wall face
 }
 
 // Both tendency kernels as ONE launch: the first half of the grid runs the (u, v) body, the second half the (w, b) body (they
@@ -891,8 +939,44 @@ __global__ void __launch_bounds__(MAXT, WAVES) k3_tile_all(Geo3 g, const real *c
                                                    const real *stamps)
 {
     const int half = gridDim.x >> 1;                 // first half of the grid: (u, v); second half: (w, b), starting as the first drains
-    if ((int)blockIdx.x >= half) tile_wb_body<TY3, KT3, NPF, NXP, FLAT, NXC, NYC>(g, cur, nxt, gm, actT, nu_kappa, dt, gam, zet, store_g, (int)blockIdx.x - half, stamps);
-    else tile_uv_body<TY3, KT3, NPF, NXP, FLAT, NXC, NYC>(g, cur, nxt, gm, nu_kappa, dt, gam, zet, store_g, (int)blockIdx.x, stamps);
+    using TG = TileGeo<TY3, KT3, NXP, FLAT, NXC, NYC>;
+    if ((int)blockIdx.x >= half) tile_wb_body<TG, NPF>(g, cur, nxt, gm, actT, nu_kappa, dt, gam, zet, store_g, (int)blockIdx.x - half, KT3, stamps);
+    else tile_uv_body<TG, NPF>(g, cur, nxt, gm, nu_kappa, dt, gam, zet, store_g, (int)blockIdx.x, KT3, stamps);
+}
+
+// ---- x- and y-tiled variant for grids wider than NXP3 columns -------------------------------------------------------------
+// The same two bodies on TileGeoX: blockDim = TX3 * TY3, 2 * B * (nx/TX3) * (ny/TY3) * (nz/levels) workgroups, LDS = 3 planes of
+// (TY3 + 6) * STR reals (host: tilex_lds_bytes, checked before the launch).  No atomics, nothing between workgroups; every loop
+// is bounded by the template constants.  `levels` (16, 8 or 4, at most KTMAX) is a kernel ARGUMENT here: one instantiation per tile
+// shape instead of one per height; the host picks the height from the grid alone (tend_shape3d).
+// Shipped shapes: TX3 = 32 (every nx % 32 == 0; a staged row is a run of
+// 38 contiguous reals, the first / last x tile's 3 halo columns from the other end of the row), TY3 = 16 (512 threads, halo share
+// 22 * 38 / 512 = 1.63, two prefetch registers per plane) where ny % 16 == 0, else TY3 = 8 (256 threads, 14 * 38 / 256 = 2.08, three).
+// A wave covers two tile rows (32 lanes each).  float64: a ds_read_b64 is served half a wave at a time and a row of 32 doubles is
+// 256 B = every bank once, so any stride is conflict-free; STR = 40.  float32: the two rows of a wave are read together and must
+// fall into different halves of the 64 banks: STR = 96 (= 32 mod 64; also conflict-free if the hardware splits the wave).
+template <int TX3> constexpr int tilex_stride() { return sizeof(real) == 4 ? 3 * TX3 : TX3 + 8; }
+template <int TX3, int TY3> constexpr int tilex_npf() { return ((TX3 + 6) * (TY3 + 6) + TX3 * TY3 - 1) / (TX3 * TY3); }
+template <int TX3, int TY3> constexpr size_t tilex_lds_bytes() { return 3 * (size_t)(TY3 + 6) * tilex_stride<TX3>() * sizeof(real); }
+
+// (no packed float32 arithmetic in this kernel: v_pk_fma_f32 and its kin are left to the kernels that were validated with them)
+#ifndef RBC_NO_PK_F32
+#if defined(__HIP_DEVICE_COMPILE__)
+#define RBC_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define RBC_NO_PK_F32
+#endif
+#endif
+template <int TX3, int TY3, int KTMAX, int WAVES>
+__global__ void RBC_NO_PK_F32 __launch_bounds__(TX3 * TY3, WAVES) k3_tilex_all(Geo3 g, const real *cur, real *nxt, real *gm, const f64 *actT,
+                                                                 const f64 *nu_kappa, real dt, real gam, real zet, int store_g,
+                                                                 int levels, const real *stamps)
+{
+    const int half = gridDim.x >> 1;
+    using TG = TileGeoX<TX3, TY3, KTMAX, tilex_stride<TX3>()>;
+    constexpr int NPF = tilex_npf<TX3, TY3>();
+    if ((int)blockIdx.x >= half) tile_wb_body<TG, NPF>(g, cur, nxt, gm, actT, nu_kappa, dt, gam, zet, store_g, (int)blockIdx.x - half, levels, stamps);
+    else tile_uv_body<TG, NPF>(g, cur, nxt, gm, nu_kappa, dt, gam, zet, store_g, (int)blockIdx.x, levels, stamps);
 }
 
 // ---- generic two-factor DFT of every line of a slab held in LDS ------------------------------------

@@ -1085,6 +1085,13 @@ int rbc_debug_launch_plan(rbc_handle *h, int groups[2])
     return RBC_OK;
 }
 
+int rbc_debug_tendency_path(rbc_handle *h, int *path)
+{
+    if (!h || !path) return fail(RBC_ERR_INVALID, "null argument");
+    *path = h->s3 ? RBC_S3(h, tendency_path3d, h) : -1;
+    return RBC_OK;
+}
+
 int rbc_debug_substeps(rbc_handle *h, const float *actions, int nsub, double dt)
 {
     if (int rc = check_handle(h)) return rc;

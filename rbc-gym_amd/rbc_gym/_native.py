@@ -96,6 +96,7 @@ SYMBOLS = {
     "rbc_debug_substeps": (C.c_int, [_vp, _fp, C.c_int, C.c_double]),
     "rbc_debug_stamps": (C.c_int, [_vp, _u64p]),
     "rbc_debug_launch_plan": (C.c_int, [_vp, _i32p]),
+    "rbc_debug_tendency_path": (C.c_int, [_vp, _i32p]),
     "rbc_reset_from_arrays3": (C.c_int, [_vp, _u8p, _dp, _dp, _dp, _dp]),
     "rbc_get_fields3": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     "rbc_debug_tendencies3": (C.c_int, [_vp, _fp, _dp, _dp, _dp, _dp]),
@@ -590,6 +591,13 @@ class NativeSim3D:
         f = np.empty(self.B, np.int32)
         self._check(self.lib.rbc_get_flags(self.h, _ptr(f, _i32p)))
         return f
+
+    def tendency_path(self):
+        """which tendency kernels a stage launches: 0 cell-per-thread, 1 z-marching, 2 full-row LDS tiles, 4 x- and y-tiled LDS tiles
+        -- include/rbc_hip.h rbc_debug_tendency_path"""
+        p = np.zeros(1, np.int32)
+        self._check(self.lib.rbc_debug_tendency_path(self.h, _ptr(p, _i32p)))
+        return int(p[0])
 
     def synchronize(self):
         self._check(self.lib.rbc_synchronize(self.h))
