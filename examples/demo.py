@@ -8,6 +8,8 @@
     python examples/demo.py checkpoint [file] [steps]   episodes from converged states (generated on the GPU if absent)
     python examples/demo.py three-d [time] [f32] [recorded]   the 3D env (f32: the float32 instantiation of the 3D kernels; recorded: the
                                                     solver-step count of the reference's recorded flowstats series)
+    python examples/demo.py flowstats [envs] [steps]   the loop of the reference's experiments/flowstats/flowstats_ra.py: Nu and max |u|, |v|, |w|
+                                                    after every env-step, from the device's statistics kernel instead of whole fields
     python examples/demo.py timing [iterations]     construction / reset / step latency of one env
 """
 import os
@@ -109,6 +111,25 @@ def three_d(args):
     env.close()
 
 
+def flowstats(args):
+    """flowstats_ra.py:52-68: zero actions, and after every env-step the Nusselt number and the velocity maxima of every env.  The
+    reference takes the maxima from the whole state on the host; flow_statistics() reads the solver's state once on the device."""
+    import numpy as np
+    n, steps = _int(args, 0, 4), _int(args, 1, 20)
+    env = gym.make_vec(ENV3D, num_envs=n, rayleigh_number=2500, heater_duration=0.25)
+    env.reset(seed=0)
+    series = []
+    for _ in range(steps):
+        _, _, _, _, info = env.step(np.zeros(env.action_space.shape, dtype=np.float32))
+        fs = env.unwrapped.flow_statistics()
+        series.append([info["nusselt"], fs["u_max"], fs["v_max"], fs["w_max"], fs["kinetic_energy"]])
+    series = np.array(series)                                            # (steps, 5, envs)
+    for name, col in zip(("Nu", "max|u|", "max|v|", "max|w|", "E_kin"), series[-1]):
+        print(f"{name:7s} after {steps} env-steps:", np.array2string(col, precision=5))
+    print("<w b>(z) of env 0, the convective part of Nu(z):", np.array2string(fs["profiles"][0, 4], precision=4))
+    env.close()
+
+
 def timing(args):
     n = _int(args, 0, 1000)
     t0 = time.perf_counter()
@@ -126,7 +147,7 @@ def timing(args):
     env.close()
 
 
-COMMANDS = {"single": single, "vector": vector, "wrapped": wrapped, "checkpoint": checkpoint, "three-d": three_d, "timing": timing}
+COMMANDS = {"single": single, "vector": vector, "wrapped": wrapped, "checkpoint": checkpoint, "three-d": three_d, "flowstats": flowstats, "timing": timing}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in COMMANDS:

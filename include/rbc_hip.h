@@ -168,6 +168,24 @@ typedef struct rbc_render3_params {
 int   rbc_render3(rbc_handle *h, const rbc_render3_params *p, const float *lut, uint8_t *out);
 void *rbc_dev_frames(rbc_handle *h);
 
+/* Horizontal statistics of the current state, computed on the device from the solver's own float64 / float32 state (never from the
+   float32 observation or state buffers: rbc_set_obs_normalization and write_state do not matter): what the reference's experiment
+   records after every env-step (max |u|, |v|, |w| next to Nu, experiments/flowstats/flowstats_ra.py:64-67) and the row-wise
+   moments of the profile pins (tests/profile_pins.py::row_moments_batch), extended to 3D.  Raw staggered values, no interpolation;
+   level k = cell level k for b, u, v and face k (the bottom face of cell k, face 0 is the wall) for w.
+   prof[e][m][k], float64 [B][6][nz]: the mean over the nx * ny cells of level k of  m = 0: b, 1: u^2, 2: v^2 (exactly 0 for dim = 2),
+   3: w^2, 4: b w (cell k times its bottom face, the product of the Nusselt sum), 5: b^2.
+   ext[e], float64 [B][5]: max |u|, max |v| (0 for dim = 2), max |w| (all nz + 1 faces), min b, max b over the env.
+   Every product and sum is formed in float64 (a float32 handle's values are converted first), so the result is a pure function of
+   what rbc_get_fields / rbc_get_fields3 return; an env's numbers do not depend on the batch.  A moment whose level holds a NaN in
+   one of its fields is NaN, and so is an extremum of a field that holds a NaN anywhere in the env (numpy's mean / max / min).
+   prof, ext: host pointers, either may be NULL (both NULL: the call returns without waiting, results stay on the device).  Runs on
+   the handle's stream behind the last step; not recorded by rbc_set_profiling.  RBC_ERR_NOT_INITIALIZED before the first reset.
+   rbc_dev_flowstats: the device buffers the last call filled, which = 0: prof, 1: ext (NULL before the first call; any other
+   `which`: NULL, and rbc_last_error says so).                                                                              */
+int   rbc_get_flowstats(rbc_handle *h, double *prof, double *ext);
+void *rbc_dev_flowstats(rbc_handle *h, int which);
+
 /* Page-locked host buffers for the rbc_get_* outputs: a pinned destination takes the float32 state copy of 1024 envs (75 MB)
    at PCIe speed.  Plain helpers over hipHostMalloc / hipHostFree; any rbc_get_* accepts either kind of pointer.  Into PAGEABLE
    memory, rbc_get_obs / rbc_get_state outputs of 8 MiB and more are staged in chunks through a page-locked buffer of the handle

@@ -7,6 +7,7 @@
 // RBC_ERR_DEVICE when HIP does.
 #include "rbc2d_instances.hpp"
 #include "rbc3d_render.hpp"
+#include "rbc_flowstats.hpp"
 
 #include "../../include/rbc_hip.h"
 
@@ -76,6 +77,7 @@ struct rbc_handle {
     uint8_t *d_frames = nullptr;       // rbc_render3: frames of the last call (grown on demand), and the caller's table
     size_t frames_cap = 0;
     float *d_lut = nullptr;
+    double *d_fs_prof = nullptr, *d_fs_ext = nullptr, *d_fs_lev = nullptr;   // rbc_get_flowstats: [B][6][nz], [B][5], per-level extrema [B][nz][5]
     uint64_t *d_seeds = nullptr;
     int *d_flags = nullptr;
     unsigned long long *d_stamps = nullptr;   // RBC_STAMPS diagnostic builds only
@@ -405,7 +407,7 @@ int rbc_destroy(rbc_handle *h)
     if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
     if (h->s3) RBC_S3(h, destroy3d, h);
     void *bufs[] = {h->d_fields, h->d_ra, h->d_tri, h->d_nu, h->d_dbg, h->d_park, h->d_celld, h->d_actions, h->d_obs, h->d_state,
-                    h->d_mask, h->d_seeds, h->d_flags, h->d_stamps, h->d_frames, h->d_lut};
+                    h->d_mask, h->d_seeds, h->d_flags, h->d_stamps, h->d_frames, h->d_lut, h->d_fs_prof, h->d_fs_ext, h->d_fs_lev};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
@@ -829,6 +831,45 @@ int rbc_render3(rbc_handle *h, const rbc_render3_params *p, const float *lut, ui
 }
 
 void *rbc_dev_frames(rbc_handle *h) { return h ? h->d_frames : nullptr; }
+
+int rbc_get_flowstats(rbc_handle *h, double *prof, double *ext)
+{
+    if (int rc = check_handle(h)) return rc;
+    if (int rc = all_initialized(h)) return rc;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    const size_t B = h->B, nz = h->nz, nprof = B * rbcfs::NSUM * nz, next = B * rbcfs::NEXT;
+    if (!h->d_fs_prof) HIP_TRY(hipMalloc(&h->d_fs_prof, nprof * sizeof(double)));
+    if (!h->d_fs_ext) HIP_TRY(hipMalloc(&h->d_fs_ext, next * sizeof(double)));
+    if (!h->d_fs_lev) HIP_TRY(hipMalloc(&h->d_fs_lev, next * nz * sizeof(double)));
+    // the state as it is NOW: the resident 2D kernel's one buffer, or the streaming path's current one of two (as rbc_get_fields3 takes it).
+    // Not recorded by the profiling events: they time env-steps (and rendered frames)
+    rbcfs::Layout L{};
+    L.nz = h->nz;
+    if (h->s3) {
+        L.n_h = h->nx * (is3d(h) ? h->cfg.ny : 1);
+        L.env_stride = RBC_S3(h, env_stride3d, h);
+        L.ou = h->ncell; L.ov = 2 * h->ncell; L.ow = 3 * h->ncell;
+        const void *st = RBC_S3(h, dev_fields3d, h);
+        if (h->s3_f32) HIP_TRY((rbcfs::launch_flowstats<float, true>(L, static_cast<const float *>(st), h->B, h->d_fs_prof, h->d_fs_lev, h->d_fs_ext, h->stream)));
+        else HIP_TRY((rbcfs::launch_flowstats<double, true>(L, static_cast<const double *>(st), h->B, h->d_fs_prof, h->d_fs_lev, h->d_fs_ext, h->stream)));
+    } else {
+        L.n_h = h->nx;
+        L.env_stride = h->env_stride;
+        L.ou = h->ncell; L.ov = 0; L.ow = 2 * h->ncell;
+        HIP_TRY((rbcfs::launch_flowstats<double, false>(L, h->d_fields, h->B, h->d_fs_prof, h->d_fs_lev, h->d_fs_ext, h->stream)));
+    }
+    if (prof) HIP_TRY(hipMemcpyAsync(prof, h->d_fs_prof, nprof * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (ext) HIP_TRY(hipMemcpyAsync(ext, h->d_fs_ext, next * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (prof || ext) HIP_TRY(hipStreamSynchronize(h->stream));
+    return RBC_OK;
+}
+
+void *rbc_dev_flowstats(rbc_handle *h, int which)
+{
+    if (!h) return nullptr;
+    if (which != 0 && which != 1) { fail(RBC_ERR_INVALID, "rbc_dev_flowstats: which must be 0 (profiles) or 1 (extrema)"); return nullptr; }
+    return which == 0 ? h->d_fs_prof : h->d_fs_ext;
+}
 
 void *rbc_host_alloc(size_t bytes)
 {

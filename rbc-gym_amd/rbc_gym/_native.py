@@ -102,6 +102,8 @@ SYMBOLS = {
     "rbc_debug_tendencies3": (C.c_int, [_vp, _fp, _dp, _dp, _dp, _dp]),
     "rbc_render3": (C.c_int, [_vp, C.POINTER(RbcRender3Params), _fp, _u8p]),
     "rbc_dev_frames": (_vp, [_vp]),
+    "rbc_get_flowstats": (C.c_int, [_vp, _dp, _dp]),
+    "rbc_dev_flowstats": (_vp, [_vp, C.c_int]),
 }
 
 _lib = None
@@ -263,7 +265,29 @@ def torch_stream_handle(stream):
     return int(stream.cuda_stream) or 1
 
 
-class NativeSim:
+class _FlowStats:
+    """get_flowstats / flowstats_views of NativeSim and NativeSim3D (include/rbc_hip.h rbc_get_flowstats)"""
+
+    def get_flowstats(self):
+        """(prof, ext), float64: prof (B, 6, nz) = per-level means of b, u^2, v^2, w^2, b w, b^2; ext (B, 5) = max |u|, max |v|,
+        max |w|, min b, max b -- computed on the device from the solver's own state"""
+        prof, ext = np.empty((self.B, 6, self.nz)), np.empty((self.B, 5))
+        self._check(self.lib.rbc_get_flowstats(self.h, _ptr(prof, _dp), _ptr(ext, _dp)))
+        return prof, ext
+
+    def flowstats_views(self):
+        """the same statistics as zero-copy torch tensors {"profiles": (B, 6, nz), "extrema": (B, 5)} over the library's device
+        buffers: the kernels are queued on the sim's stream and nothing is copied or waited for -- `synchronize()` (or an event)
+        before another stream reads them.  The tensors are rewritten by the next call."""
+        import torch
+        from .vector import DeviceArray
+        self._check(self.lib.rbc_get_flowstats(self.h, None, None))
+        dev = f"cuda:{self.cfg.device}"
+        return {"profiles": torch.as_tensor(DeviceArray(self.lib.rbc_dev_flowstats(self.h, 0), (self.B, 6, self.nz), "<f8", self), device=dev),
+                "extrema": torch.as_tensor(DeviceArray(self.lib.rbc_dev_flowstats(self.h, 1), (self.B, 5), "<f8", self), device=dev)}
+
+
+class NativeSim(_FlowStats):
     """A batch of B envs on one GPU.  Method names follow the reference's Julia API
     (rbc_sim2D_api.jl): initialize_simulation -> reset*, step_simulation -> step, get_state,
     get_observation, get_info, get_nusselt."""
@@ -433,7 +457,7 @@ class NativeSim:
                     flags=L.rbc_dev_flags(self.h), fields=L.rbc_dev_fields(self.h))
 
 
-class NativeSim3D:
+class NativeSim3D(_FlowStats):
     """A batch of B 3D envs on one GPU (rbc_sim3D_api.jl semantics; array shapes (nz, ny, nx))."""
 
     def __init__(self, batch=1, device=0, shape=(16, 32, 32), domain=(2.0, 4 * np.pi, 4 * np.pi), ra=2500.0, pr=0.7,

@@ -116,6 +116,18 @@ class _Window:
             self.screen = None
 
 
+def flow_statistics_dict(prof, ext, single=False):
+    """(prof, ext) of `get_flowstats()` under names: "profiles" (B, 6, nz) -- per-level means of b, u^2, v^2, w^2, b w, b^2 --,
+    "u_max", "v_max", "w_max", "b_min", "b_max" (B,) and "kinetic_energy" = 1/2 mean over the levels of <u^2> + <v^2> + <w^2>;
+    single: one env, without the batch axis"""
+    out = {"profiles": prof, "kinetic_energy": 0.5 * (prof[:, 1] + prof[:, 2] + prof[:, 3]).mean(axis=1)}
+    for j, name in enumerate(("u_max", "v_max", "w_max", "b_min", "b_max")):
+        out[name] = ext[:, j].copy()
+    if single:
+        out = {k: (v[0] if k == "profiles" else float(v[0])) for k, v in out.items()}
+    return out
+
+
 class NativeEnvBase(gym.Env):
     """One env = a batch-of-one simulation handle.  Subclasses provide `_fields` (dataset names of a checkpoint
     episode), `_observe()`, `_info()` and `_reward()`."""
@@ -177,6 +189,11 @@ class NativeEnvBase(gym.Env):
         self.last_obs, self.last_reward, self.last_info = self._observe(), self._reward(), self._info()
         truncated = bool(self.last_info["t"] >= self.episode_length)
         return self.last_obs, self.last_reward, False, truncated, self.last_info      # there is no terminal state
+
+    def flow_statistics(self):
+        """Horizontal statistics of the current state, computed on the device (include/rbc_hip.h rbc_get_flowstats; what the
+        reference's experiments/flowstats/flowstats_ra.py:64-67 takes from whole fields on the host): see flow_statistics_dict"""
+        return flow_statistics_dict(*self.sim.get_flowstats(), single=True)
 
     # ---- teardown --------------------------------------------------------------------------------
     def close(self):

@@ -138,6 +138,9 @@ class ShardedSim:
     def get_flags(self):
         return self._cat(self._all(lambda r, sim: sim.get_flags()))
 
+    def get_flowstats(self):
+        return self._cat(self._all(lambda r, sim: tuple(sim.get_flowstats())))
+
     def get_cell_distances(self, *a):
         return self._cat(self._all(lambda r, sim: sim.get_cell_distances(*a)))
 

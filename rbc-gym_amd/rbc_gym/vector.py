@@ -16,7 +16,7 @@ from ._gym import gym
 from . import _native
 from .checkpoint import read_checkpoint
 from .sharded import ShardedSim
-from .envs._common import check_checkpoint_grid, checkpoint_index
+from .envs._common import check_checkpoint_grid, checkpoint_index, flow_statistics_dict
 from .envs.rbc2D import build_spaces, sim_kwargs
 
 
@@ -116,6 +116,11 @@ class _BatchedEnv(gym.vector.VectorEnv):
         `self.sim.synchronize()` (or an event) before another stream reads the device views.  With devices=[...]: a
         list of pointers, one per shard, each on that shard's GPU."""
         self.sim.step_dev(actions_device_ptr)
+
+    def flow_statistics(self):
+        """Horizontal statistics of every env's current state, computed on the device from the solver's own state (observation
+        normalisation does not touch them); with devices=[...] the shards' results in env order.  See flow_statistics_dict."""
+        return flow_statistics_dict(*self.sim.get_flowstats())
 
     def _pooled(self, shape, mode):
         """destination for a large host output: a page-locked array nobody else references (None: let the getter allocate)"""
