@@ -10,6 +10,8 @@
                                                     solver-step count of the reference's recorded flowstats series)
     python examples/demo.py flowstats [envs] [steps]   the loop of the reference's experiments/flowstats/flowstats_ra.py: Nu and max |u|, |v|, |w|
                                                     after every env-step, from the device's statistics kernel instead of whole fields
+    python examples/demo.py spectra [envs] [steps]     horizontal power spectra of the 3D envs from the device's spectra kernels: mid-level
+                                                    b and w power of the first modes along x and along y
     python examples/demo.py timing [iterations]     construction / reset / step latency of one env
 """
 import os
@@ -130,6 +132,24 @@ def flowstats(args):
     env.close()
 
 
+def spectra(args):
+    """rolls may align along x or along y: the power of b and w at mid-height, mode by mode, in both directions"""
+    import numpy as np
+    n, steps = _int(args, 0, 4), _int(args, 1, 20)
+    env = gym.make_vec(ENV3D, num_envs=n, rayleigh_number=2500, heater_duration=0.25)
+    env.reset(seed=0)
+    for _ in range(steps):
+        env.step(np.zeros(env.action_space.shape, dtype=np.float32))
+    sp = env.unwrapped.power_spectra()
+    mid = sp["x"].shape[2] // 2
+    for axis, k in (("x", "kx"), ("y", "ky")):
+        print(f"k{axis} of the first modes:", np.array2string(sp[k][:6], precision=3))
+        for name in ("b", "w"):
+            ch = sp["channels"].index(name)
+            print(f"  {name} power along {axis} at level {mid}, env 0:", np.array2string(sp[axis][0, ch, mid, :6], precision=3))
+    env.close()
+
+
 def timing(args):
     n = _int(args, 0, 1000)
     t0 = time.perf_counter()
@@ -147,7 +167,7 @@ def timing(args):
     env.close()
 
 
-COMMANDS = {"single": single, "vector": vector, "wrapped": wrapped, "checkpoint": checkpoint, "three-d": three_d, "flowstats": flowstats, "timing": timing}
+COMMANDS = {"single": single, "vector": vector, "wrapped": wrapped, "checkpoint": checkpoint, "three-d": three_d, "flowstats": flowstats, "spectra": spectra, "timing": timing}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in COMMANDS:

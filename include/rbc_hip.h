@@ -186,6 +186,28 @@ void *rbc_dev_frames(rbc_handle *h);
 int   rbc_get_flowstats(rbc_handle *h, double *prof, double *ext);
 void *rbc_dev_flowstats(rbc_handle *h, int which);
 
+/* Horizontal power and co-spectra of the current state, level by level, computed on the device from the same buffer and under the
+   same conventions as rbc_get_flowstats (raw staggered values; level k = cell level k of b, u, v and face k, the bottom face of cell
+   k, of w; float64 throughout, a float32 state is widened first).  DESIGN.md section 3e.
+   Line transform of row j of a level: F_j[m] = (1/nx) sum_i f[j][i] e^{-2 pi i m i / nx}, m = 0 .. nx/2 (numpy's rfft / nx); one-sided
+   weights c_0 = 1, c_m = 2, c_{nx/2} = 1 for even nx.
+   px[e][ch][k][m], float64 [B][6][nz][nx/2 + 1]:  ch 0: c_m mean_j |B_j[m]|^2;  1, 2, 3: the same for u, v (exactly 0 on a dim = 2
+   handle: written, not computed), w;  4: co-spectrum c_m mean_j Re (B_j[m] conj W_j[m]);  5: quadrature spectrum, Im of the same.
+   sum_m of ch 0, 1, 2, 3, 4 = prof[e][5, 1, 2, 3, 4][k] of rbc_get_flowstats (Parseval); for ny = 1, ch 4 and 5 over sqrt(ch 0 ch 3)
+   are the cos and sin of the b-w cross phase.
+   py[e][ch][k][n], float64 [B][6][nz][ny/2 + 1], dim = 3 only: the same six with the transform along y and the mean over x.
+   NaN: b and w are transformed as one complex line, u and v as another, so a NaN in b or w of a level makes channels 0, 3, 4, 5 of
+   that level NaN at every mode (in px and py), one in u or v channels 1 and 2 (dim = 2: 1 only); nothing else changes by a bit.
+   (numpy would keep the partner's channel finite.)  An env's numbers do not depend on the batch.
+   px, py: host pointers, either may be NULL (both NULL: the call returns without waiting, results stay on the device).  Runs on the
+   handle's stream behind the last step; not recorded by rbc_set_profiling.  RBC_ERR_NOT_INITIALIZED before the first reset;
+   RBC_ERR_INVALID for a non-NULL py on a dim = 2 handle, and where the two complex line sets of one row (one column) do not fit
+   the 160 KB of LDS (nx, ny <= ~1500).
+   rbc_dev_spectra: the device buffers the last call filled, which = 0: px, 1: py (NULL before the first call and for py of a
+   dim = 2 handle; any other `which`: NULL, and rbc_last_error says so).                                                      */
+int   rbc_get_spectra(rbc_handle *h, double *px, double *py);
+void *rbc_dev_spectra(rbc_handle *h, int which);
+
 /* Page-locked host buffers for the rbc_get_* outputs: a pinned destination takes the float32 state copy of 1024 envs (75 MB)
    at PCIe speed.  Plain helpers over hipHostMalloc / hipHostFree; any rbc_get_* accepts either kind of pointer.  Into PAGEABLE
    memory, rbc_get_obs / rbc_get_state outputs of 8 MiB and more are staged in chunks through a page-locked buffer of the handle

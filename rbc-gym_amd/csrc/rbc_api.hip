@@ -8,6 +8,7 @@
 #include "rbc2d_instances.hpp"
 #include "rbc3d_render.hpp"
 #include "rbc_flowstats.hpp"
+#include "rbc_spectra.hpp"
 
 #include "../../include/rbc_hip.h"
 
@@ -78,6 +79,8 @@ struct rbc_handle {
     size_t frames_cap = 0;
     float *d_lut = nullptr;
     double *d_fs_prof = nullptr, *d_fs_ext = nullptr, *d_fs_lev = nullptr;   // rbc_get_flowstats: [B][6][nz], [B][5], per-level extrema [B][nz][5]
+    double *d_sp_px = nullptr, *d_sp_py = nullptr;   // rbc_get_spectra: [B][6][nz][nx/2 + 1], [B][6][nz][ny/2 + 1] (dim = 3)
+    rbcsp::cplx *d_sp_tw = nullptr;                  // ... its float64 twiddles [nx + ny] (a float32 handle's plan has float ones, a resident 2D handle none)
     uint64_t *d_seeds = nullptr;
     int *d_flags = nullptr;
     unsigned long long *d_stamps = nullptr;   // RBC_STAMPS diagnostic builds only
@@ -407,7 +410,7 @@ int rbc_destroy(rbc_handle *h)
     if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
     if (h->s3) RBC_S3(h, destroy3d, h);
     void *bufs[] = {h->d_fields, h->d_ra, h->d_tri, h->d_nu, h->d_dbg, h->d_park, h->d_celld, h->d_actions, h->d_obs, h->d_state,
-                    h->d_mask, h->d_seeds, h->d_flags, h->d_stamps, h->d_frames, h->d_lut, h->d_fs_prof, h->d_fs_ext, h->d_fs_lev};
+                    h->d_mask, h->d_seeds, h->d_flags, h->d_stamps, h->d_frames, h->d_lut, h->d_fs_prof, h->d_fs_ext, h->d_fs_lev, h->d_sp_px, h->d_sp_py, h->d_sp_tw};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
@@ -869,6 +872,66 @@ void *rbc_dev_flowstats(rbc_handle *h, int which)
     if (!h) return nullptr;
     if (which != 0 && which != 1) { fail(RBC_ERR_INVALID, "rbc_dev_flowstats: which must be 0 (profiles) or 1 (extrema)"); return nullptr; }
     return which == 0 ? h->d_fs_prof : h->d_fs_ext;
+}
+
+int rbc_get_spectra(rbc_handle *h, double *px, double *py)
+{
+    if (int rc = check_handle(h)) return rc;
+    if (int rc = all_initialized(h)) return rc;
+    const bool d3 = is3d(h);
+    if (!d3 && py) return fail(RBC_ERR_INVALID, "rbc_get_spectra: a dim=2 handle has no y spectra (py must be NULL)");
+    rbcsp::Layout L{};
+    L.nx = h->nx; L.ny = d3 ? h->cfg.ny : 1; L.nz = h->nz;
+    // every LDS size is known here, before anything is allocated or launched
+    rbcsp::Plan X = rbcsp::plan_x(L.nx, L.ny, L.nz), Y{};
+    host3::factor2(L.nx, X.n1, X.n2);
+    if (X.lds > rbcsp::LDS_CEILING)
+        return fail(RBC_ERR_INVALID, "rbc_get_spectra: the two line sets of one row do not fit the 160 KB of LDS (nx <= ~1500)");
+    if (d3) {
+        Y = rbcsp::plan_y(L.nx, L.ny);
+        host3::factor2(L.ny, Y.n1, Y.n2);
+        if (Y.lds > rbcsp::LDS_CEILING)
+            return fail(RBC_ERR_INVALID, "rbc_get_spectra: the two line sets of one column do not fit the 160 KB of LDS (ny <= ~1500)");
+    }
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    const size_t nlev = (size_t)h->B * rbcsp::NCH * L.nz, npx = nlev * (L.nx / 2 + 1), npy = d3 ? nlev * (L.ny / 2 + 1) : 0;
+    if (!h->d_sp_px) HIP_TRY(hipMalloc(&h->d_sp_px, npx * sizeof(double)));
+    if (d3 && !h->d_sp_py) HIP_TRY(hipMalloc(&h->d_sp_py, npy * sizeof(double)));
+    const bool first = !h->d_sp_tw;
+    if (first) {
+        rbcsp::cplx *tw = nullptr;
+        HIP_TRY(hipMalloc(&tw, (size_t)(L.nx + L.ny) * sizeof(rbcsp::cplx)));
+        hipLaunchKernelGGL(rbc3::k3_twiddles, dim3((unsigned)((L.nx + L.ny + 127) / 128)), dim3(128), 0, h->stream, tw, L.nx, L.ny);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { (void)hipFree(tw); return fail(RBC_ERR_DEVICE, std::string("k3_twiddles: ") + hipGetErrorString(e)); }
+        h->d_sp_tw = tw;
+    }
+    // the state as it is NOW, taken the way rbc_get_flowstats takes it; not recorded by the profiling events.  A 2D handle never reads a
+    // v block (the streaming layout's is zeros): channel 2 is written as 0
+    if (h->s3) {
+        L.env_stride = RBC_S3(h, env_stride3d, h);
+        L.ou = h->ncell; L.ov = 2 * h->ncell; L.ow = 3 * h->ncell;
+        const void *st = RBC_S3(h, dev_fields3d, h);
+        if (h->s3_f32 && d3) HIP_TRY((rbcsp::launch_spectra<float, true>(first, L, X, Y, static_cast<const float *>(st), h->B, h->d_sp_tw, h->d_sp_px, h->d_sp_py, h->stream)));
+        else if (h->s3_f32) HIP_TRY((rbcsp::launch_spectra<float, false>(first, L, X, Y, static_cast<const float *>(st), h->B, h->d_sp_tw, h->d_sp_px, h->d_sp_py, h->stream)));
+        else if (d3) HIP_TRY((rbcsp::launch_spectra<double, true>(first, L, X, Y, static_cast<const double *>(st), h->B, h->d_sp_tw, h->d_sp_px, h->d_sp_py, h->stream)));
+        else HIP_TRY((rbcsp::launch_spectra<double, false>(first, L, X, Y, static_cast<const double *>(st), h->B, h->d_sp_tw, h->d_sp_px, h->d_sp_py, h->stream)));
+    } else {
+        L.env_stride = h->env_stride;
+        L.ou = h->ncell; L.ov = 0; L.ow = 2 * h->ncell;
+        HIP_TRY((rbcsp::launch_spectra<double, false>(first, L, X, Y, h->d_fields, h->B, h->d_sp_tw, h->d_sp_px, h->d_sp_py, h->stream)));
+    }
+    if (px) HIP_TRY(hipMemcpyAsync(px, h->d_sp_px, npx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (py) HIP_TRY(hipMemcpyAsync(py, h->d_sp_py, npy * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (px || py) HIP_TRY(hipStreamSynchronize(h->stream));
+    return RBC_OK;
+}
+
+void *rbc_dev_spectra(rbc_handle *h, int which)
+{
+    if (!h) return nullptr;
+    if (which != 0 && which != 1) { fail(RBC_ERR_INVALID, "rbc_dev_spectra: which must be 0 (x spectra) or 1 (y spectra)"); return nullptr; }
+    return which == 0 ? h->d_sp_px : h->d_sp_py;
 }
 
 void *rbc_host_alloc(size_t bytes)

@@ -104,6 +104,8 @@ SYMBOLS = {
     "rbc_dev_frames": (_vp, [_vp]),
     "rbc_get_flowstats": (C.c_int, [_vp, _dp, _dp]),
     "rbc_dev_flowstats": (_vp, [_vp, C.c_int]),
+    "rbc_get_spectra": (C.c_int, [_vp, _dp, _dp]),
+    "rbc_dev_spectra": (_vp, [_vp, C.c_int]),
 }
 
 _lib = None
@@ -287,7 +289,39 @@ class _FlowStats:
                 "extrema": torch.as_tensor(DeviceArray(self.lib.rbc_dev_flowstats(self.h, 1), (self.B, 5), "<f8", self), device=dev)}
 
 
-class NativeSim(_FlowStats):
+class _Spectra:
+    """get_spectra / spectra_views of NativeSim and NativeSim3D (include/rbc_hip.h rbc_get_spectra)"""
+
+    def _spectra_shapes(self):
+        ny = getattr(self, "ny", None)
+        return (self.B, 6, self.nz, self.nx // 2 + 1), (None if ny is None else (self.B, 6, self.nz, ny // 2 + 1))
+
+    def get_spectra(self):
+        """(px, py), float64: px (B, 6, nz, nx//2 + 1) = one-sided x spectra per level, averaged over y -- power of b, u, v, w, then
+        the co- and the quadrature spectrum of (b, w) --, py (B, 6, nz, ny//2 + 1) the same along y (None for a 2D sim); computed
+        on the device from the solver's own state"""
+        sx, sy = self._spectra_shapes()
+        px, py = np.empty(sx), (None if sy is None else np.empty(sy))
+        self._check(self.lib.rbc_get_spectra(self.h, _ptr(px, _dp), None if py is None else _ptr(py, _dp)))
+        return px, py
+
+    def spectra_views(self):
+        """the same spectra as zero-copy torch tensors {"x": ..., "y": ...} (no "y" for a 2D sim) over the library's device buffers,
+        under the rules of flowstats_views: queued on the sim's stream, nothing copied or waited for, rewritten by the next call"""
+        import torch
+        from .vector import DeviceArray
+        self._check(self.lib.rbc_get_spectra(self.h, None, None))
+        dev = f"cuda:{self.cfg.device}"
+        return {name: torch.as_tensor(DeviceArray(self.lib.rbc_dev_spectra(self.h, which), shape, "<f8", self), device=dev)
+                for which, (name, shape) in enumerate(zip(("x", "y"), self._spectra_shapes())) if shape is not None}
+
+    def spectra_axes(self):
+        """(kx, ky): the wavenumbers 2 pi m / lx of px's last axis and 2 pi n / ly of py's (None for a 2D sim)"""
+        ny = getattr(self, "ny", None)
+        return (2 * np.pi * np.arange(self.nx // 2 + 1) / self.cfg.lx, None if ny is None else 2 * np.pi * np.arange(ny // 2 + 1) / self.cfg.ly)
+
+
+class NativeSim(_FlowStats, _Spectra):
     """A batch of B envs on one GPU.  Method names follow the reference's Julia API
     (rbc_sim2D_api.jl): initialize_simulation -> reset*, step_simulation -> step, get_state,
     get_observation, get_info, get_nusselt."""
@@ -457,7 +491,7 @@ class NativeSim(_FlowStats):
                     flags=L.rbc_dev_flags(self.h), fields=L.rbc_dev_fields(self.h))
 
 
-class NativeSim3D(_FlowStats):
+class NativeSim3D(_FlowStats, _Spectra):
     """A batch of B 3D envs on one GPU (rbc_sim3D_api.jl semantics; array shapes (nz, ny, nx))."""
 
     def __init__(self, batch=1, device=0, shape=(16, 32, 32), domain=(2.0, 4 * np.pi, 4 * np.pi), ra=2500.0, pr=0.7,

@@ -128,6 +128,20 @@ def flow_statistics_dict(prof, ext, single=False):
     return out
 
 
+SPECTRA_CHANNELS = ("b", "u", "v", "w", "bw_co", "bw_quad")
+
+
+def power_spectra_dict(sim, single=False):
+    """`sim.get_spectra()` under names: "x" (B, 6, nz, nx//2 + 1) and "y" (B, 6, nz, ny//2 + 1; None for 2D) -- one-sided power of
+    b, u, v, w and the co- and quadrature spectrum of (b, w) per level, include/rbc_hip.h rbc_get_spectra --, the wavenumbers "kx" =
+    2 pi m / Lx and "ky" = 2 pi n / Ly (None for 2D) and the channel names; single: one env, without the batch axis"""
+    px, py = sim.get_spectra()
+    kx, ky = sim.spectra_axes()
+    if single:
+        px, py = px[0], (None if py is None else py[0])
+    return {"x": px, "y": py, "kx": kx, "ky": ky, "channels": SPECTRA_CHANNELS}
+
+
 class NativeEnvBase(gym.Env):
     """One env = a batch-of-one simulation handle.  Subclasses provide `_fields` (dataset names of a checkpoint
     episode), `_observe()`, `_info()` and `_reward()`."""
@@ -194,6 +208,10 @@ class NativeEnvBase(gym.Env):
         """Horizontal statistics of the current state, computed on the device (include/rbc_hip.h rbc_get_flowstats; what the
         reference's experiments/flowstats/flowstats_ra.py:64-67 takes from whole fields on the host): see flow_statistics_dict"""
         return flow_statistics_dict(*self.sim.get_flowstats(), single=True)
+
+    def power_spectra(self):
+        """Horizontal power and co-spectra of the current state, level by level, computed on the device: see power_spectra_dict"""
+        return power_spectra_dict(self.sim, single=True)
 
     # ---- teardown --------------------------------------------------------------------------------
     def close(self):

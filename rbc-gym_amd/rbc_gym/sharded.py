@@ -141,6 +141,15 @@ class ShardedSim:
     def get_flowstats(self):
         return self._cat(self._all(lambda r, sim: tuple(sim.get_flowstats())))
 
+    def get_spectra(self):
+        parts = self._all(lambda r, sim: tuple(sim.get_spectra()))
+        if parts[0][1] is None:                              # 2D sims have no y spectra
+            return self._cat([p[0] for p in parts]), None
+        return self._cat(parts)
+
+    def spectra_axes(self):
+        return self.sims[0].spectra_axes()
+
     def get_cell_distances(self, *a):
         return self._cat(self._all(lambda r, sim: sim.get_cell_distances(*a)))
 

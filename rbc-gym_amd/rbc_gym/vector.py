@@ -16,7 +16,7 @@ from ._gym import gym
 from . import _native
 from .checkpoint import read_checkpoint
 from .sharded import ShardedSim
-from .envs._common import check_checkpoint_grid, checkpoint_index, flow_statistics_dict
+from .envs._common import check_checkpoint_grid, checkpoint_index, flow_statistics_dict, power_spectra_dict
 from .envs.rbc2D import build_spaces, sim_kwargs
 
 
@@ -121,6 +121,11 @@ class _BatchedEnv(gym.vector.VectorEnv):
         """Horizontal statistics of every env's current state, computed on the device from the solver's own state (observation
         normalisation does not touch them); with devices=[...] the shards' results in env order.  See flow_statistics_dict."""
         return flow_statistics_dict(*self.sim.get_flowstats())
+
+    def power_spectra(self):
+        """Horizontal power and co-spectra of every env's current state, level by level, computed on the device from the solver's own
+        state; with devices=[...] the shards' results in env order.  See power_spectra_dict."""
+        return power_spectra_dict(self.sim)
 
     def _pooled(self, shape, mode):
         """destination for a large host output: a page-locked array nobody else references (None: let the getter allocate)"""
