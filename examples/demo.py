@@ -12,6 +12,8 @@
                                                     after every env-step, from the device's statistics kernel instead of whole fields
     python examples/demo.py spectra [envs] [steps]     horizontal power spectra of the 3D envs from the device's spectra kernels: mid-level
                                                     b and w power of the first modes along x and along y
+    python examples/demo.py dissipation [envs] [steps] the flux Nusselt number next to the two dissipation-based ones, from the device's
+                                                    gradient-statistics kernel
     python examples/demo.py timing [iterations]     construction / reset / step latency of one env
 """
 import os
@@ -150,6 +152,26 @@ def spectra(args):
     env.close()
 
 
+def dissipation(args):
+    """the three Nusselt numbers side by side: the flux one of the info dict and the two from the dissipation rates (they agree only in a
+    statistically steady state under uniform plates: zero actions)"""
+    import numpy as np
+    n, steps = _int(args, 0, 4), _int(args, 1, 40)
+    env = gym.make_vec(ENV3D, num_envs=n, rayleigh_number=2500, heater_duration=0.25)
+    env.reset(seed=0)
+    for _ in range(steps):
+        _, _, _, _, info = env.step(np.zeros(env.action_space.shape, dtype=np.float32))
+    d = env.unwrapped.dissipation_rates()
+    # info["nusselt"] of the 3D env is the reference's 1 + <w b'> / kappa; in units of the conductive flux kappa delta_b / lz the convective
+    # part carries the factor lz / delta_b (2 for the default domain)
+    lz, (b_top, b_bottom) = env.unwrapped.domain[0], env.unwrapped.temperature_difference
+    flux = 1 + (np.asarray(info["nusselt"]) - 1) * lz / (b_bottom - b_top)
+    for name, col in (("Nu (flux)", flux), ("Nu (eps_T)", d["nusselt_thermal"]), ("Nu (eps_u)", d["nusselt_viscous"])):
+        print(f"{name:11s} after {steps} env-steps:", np.array2string(np.asarray(col), precision=5))
+    print("<(dz b)^2>(z) of env 0, the boundary layers:", np.array2string(d["faces"][0, 0], precision=3))
+    env.close()
+
+
 def timing(args):
     n = _int(args, 0, 1000)
     t0 = time.perf_counter()
@@ -167,7 +189,8 @@ def timing(args):
     env.close()
 
 
-COMMANDS = {"single": single, "vector": vector, "wrapped": wrapped, "checkpoint": checkpoint, "three-d": three_d, "flowstats": flowstats, "spectra": spectra, "timing": timing}
+COMMANDS = {"single": single, "vector": vector, "wrapped": wrapped, "checkpoint": checkpoint, "three-d": three_d, "flowstats": flowstats, "spectra": spectra, "dissipation": dissipation,
+            "timing": timing}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in COMMANDS:

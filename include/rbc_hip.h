@@ -208,6 +208,37 @@ void *rbc_dev_flowstats(rbc_handle *h, int which);
 int   rbc_get_spectra(rbc_handle *h, double *px, double *py);
 void *rbc_dev_spectra(rbc_handle *h, int which);
 
+/* Dissipation rates and velocity-gradient statistics of the current state, level by level, computed on the device from the same
+   buffer and under the same conventions as rbc_get_flowstats (float64 throughout, a float32 state is widened first; the float32
+   observation and state buffers are never read).  DESIGN.md section 3f.
+   Grid: uniform, dx = lx/nx, dy = ly/ny, dz = lz/nz; u[i] the west face of cell i, v[j] the south face, w[k] the bottom face of
+   cell k; x and y periodic.  Difference quotients at their natural staggered places:
+     on level k = 0 .. nz-1:  dx b = (b[i] - b[i-1])/dx on x-faces, dy b on y-faces;  dx u = (u[i+1] - u[i])/dx, dy v and
+                              dz w = (w[k+1] - w[k])/dz at centres;  dy u = (u[j] - u[j-1])/dy and dx v = (v[i] - v[i-1])/dx on xy-edges;
+     on z-face k = 0 .. nz:   dz b = (b[k] - b[k-1])/dz;  dz u and dx w = (w[k][i] - w[k][i-1])/dx on xz-edges;  dz v and dy w on yz-edges;
+     at the walls (no-slip, fixed temperature):  dz u = 2 u[0]/dz at face 0, -2 u[nz-1]/dz at face nz (likewise v);  w's wall faces
+                              are what the state holds;  dz b = 2 (b[0] - wall_b)/dz at face 0, 2 (min_b - b[nz-1])/dz at face nz.
+   wall_b: the bottom plate's temperature, float64 [B][ny][nx] on the host (ny = 1 for dim = 2); NULL = the uniform plate
+   min_b + delta_b.  (The handle does not know the heater profile of the last step; the call does not guess it.)
+   Outputs, means over the nx * ny points of a level; no viscosity or diffusivity enters:
+     cells[e][c][k], float64 [B][4][nz]:    c = 0: (dx b)^2 + (dy b)^2;  1: (dx u)^2 + (dy v)^2 + (dz w)^2;  2: (dy u)^2 + (dx v)^2;
+                                            3: dy u dx v
+     faces[e][f][k], float64 [B][5][nz+1]:  f = 0: (dz b)^2;  1: (dz u)^2 + (dx w)^2;  2: dz u dx w;  3: (dz v)^2 + (dy w)^2;  4: dz v dy w
+     tot[e][0..3], float64 [B][4]: volume means, every level with weight 1/nz, faces 0 and nz with half of it:
+                                            0: |grad b|^2 = cells 0 + faces 0;  1: normal part, cells 1;  2: shear part, cells 2 +
+                                            faces 1 + faces 3;  3: cross part, cells 3 + faces 2 + faces 4
+   so that  eps_T = kappa tot0,  eps_u = nu (tot1 + tot2)  (strain form: nu (2 tot1 + tot2 + 2 tot3)),  enstrophy = tot2 - 2 tot3.
+   On a dim = 2 handle every y-derivative and every v term is an exact zero, written and not computed (cells 2, 3 and faces 3, 4;
+   cells 0, 1 lose their y parts); no v block is read.  A NaN makes NaN exactly the levels and faces whose stencil touches it, and tot
+   through them; nothing else changes by a bit.  An env's numbers do not depend on the batch.
+   cells, faces, tot: host pointers, any may be NULL (all NULL: the call returns without waiting, results stay on the device).  Runs
+   on the handle's stream behind the last step; not recorded by rbc_set_profiling.  RBC_ERR_NOT_INITIALIZED before the first reset;
+   RBC_ERR_INVALID where one row of a level does not fit a workgroup (nx > 2048), checked before anything is launched.
+   rbc_dev_dissipation: the device buffers the last call filled, which = 0: cells, 1: faces, 2: tot (NULL before the first call; any
+   other `which`: NULL, and rbc_last_error says so).                                                                          */
+int   rbc_get_dissipation(rbc_handle *h, const double *wall_b, double *cells, double *faces, double *tot);
+void *rbc_dev_dissipation(rbc_handle *h, int which);
+
 /* Page-locked host buffers for the rbc_get_* outputs: a pinned destination takes the float32 state copy of 1024 envs (75 MB)
    at PCIe speed.  Plain helpers over hipHostMalloc / hipHostFree; any rbc_get_* accepts either kind of pointer.  Into PAGEABLE
    memory, rbc_get_obs / rbc_get_state outputs of 8 MiB and more are staged in chunks through a page-locked buffer of the handle

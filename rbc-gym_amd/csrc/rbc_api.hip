@@ -9,6 +9,7 @@
 #include "rbc3d_render.hpp"
 #include "rbc_flowstats.hpp"
 #include "rbc_spectra.hpp"
+#include "rbc_dissipation.hpp"
 
 #include "../../include/rbc_hip.h"
 
@@ -81,6 +82,8 @@ struct rbc_handle {
     double *d_fs_prof = nullptr, *d_fs_ext = nullptr, *d_fs_lev = nullptr;   // rbc_get_flowstats: [B][6][nz], [B][5], per-level extrema [B][nz][5]
     double *d_sp_px = nullptr, *d_sp_py = nullptr;   // rbc_get_spectra: [B][6][nz][nx/2 + 1], [B][6][nz][ny/2 + 1] (dim = 3)
     rbcsp::cplx *d_sp_tw = nullptr;                  // ... its float64 twiddles [nx + ny] (a float32 handle's plan has float ones, a resident 2D handle none)
+    double *d_ds_cells = nullptr, *d_ds_faces = nullptr, *d_ds_tot = nullptr;   // rbc_get_dissipation: [B][4][nz], [B][5][nz + 1], [B][4]
+    double *d_ds_part = nullptr, *d_ds_wall = nullptr;                          // ... strip partials [B][strips][9][nz + 1], the caller's wall_b [B][ny][nx]
     uint64_t *d_seeds = nullptr;
     int *d_flags = nullptr;
     unsigned long long *d_stamps = nullptr;   // RBC_STAMPS diagnostic builds only
@@ -410,7 +413,8 @@ int rbc_destroy(rbc_handle *h)
     if (h->own_stream) (void)hipStreamSynchronize(h->own_stream);
     if (h->s3) RBC_S3(h, destroy3d, h);
     void *bufs[] = {h->d_fields, h->d_ra, h->d_tri, h->d_nu, h->d_dbg, h->d_park, h->d_celld, h->d_actions, h->d_obs, h->d_state,
-                    h->d_mask, h->d_seeds, h->d_flags, h->d_stamps, h->d_frames, h->d_lut, h->d_fs_prof, h->d_fs_ext, h->d_fs_lev, h->d_sp_px, h->d_sp_py, h->d_sp_tw};
+                    h->d_mask, h->d_seeds, h->d_flags, h->d_stamps, h->d_frames, h->d_lut, h->d_fs_prof, h->d_fs_ext, h->d_fs_lev, h->d_sp_px, h->d_sp_py, h->d_sp_tw,
+                    h->d_ds_cells, h->d_ds_faces, h->d_ds_tot, h->d_ds_part, h->d_ds_wall};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
@@ -932,6 +936,52 @@ void *rbc_dev_spectra(rbc_handle *h, int which)
     if (!h) return nullptr;
     if (which != 0 && which != 1) { fail(RBC_ERR_INVALID, "rbc_dev_spectra: which must be 0 (x spectra) or 1 (y spectra)"); return nullptr; }
     return which == 0 ? h->d_sp_px : h->d_sp_py;
+}
+
+int rbc_get_dissipation(rbc_handle *h, const double *wall_b, double *cells, double *faces, double *tot)
+{
+    if (int rc = check_handle(h)) return rc;
+    if (int rc = all_initialized(h)) return rc;
+    const int ny = is3d(h) ? h->cfg.ny : 1;
+    // every size is known here, before anything is allocated or launched
+    rbcds::Plan P{};
+    if (!rbcds::make_plan(P, h->nx, ny, h->nz, (h->s3 && h->s3_f32) ? sizeof(float) : sizeof(double), h->s3 != nullptr))
+        return fail(RBC_ERR_INVALID, "rbc_get_dissipation: one row of the level and its halo row do not fit a workgroup's registers and LDS (nx <= 2048)");
+    P.rdx = 1.0 / (h->cfg.lx / h->nx); P.rdy = is3d(h) ? 1.0 / (h->cfg.ly / ny) : 0.0; P.rdz = 1.0 / (h->cfg.lz / h->nz);
+    P.min_b = h->cfg.min_b; P.wall_b = h->cfg.min_b + h->cfg.delta_b;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    const size_t B = h->B, nz = h->nz, ncells = B * rbcds::NCELL * nz, nfaces = B * rbcds::NFACE * (nz + 1), ntot = B * 4, nwall = B * P.n_h;
+    if (!h->d_ds_cells) HIP_TRY(hipMalloc(&h->d_ds_cells, ncells * sizeof(double)));
+    if (!h->d_ds_faces) HIP_TRY(hipMalloc(&h->d_ds_faces, nfaces * sizeof(double)));
+    if (!h->d_ds_tot) HIP_TRY(hipMalloc(&h->d_ds_tot, ntot * sizeof(double)));
+    if (!h->d_ds_part) HIP_TRY(hipMalloc(&h->d_ds_part, B * P.nstrips * rbcds::NCH * (nz + 1) * sizeof(double)));
+    if (!h->d_ds_wall) HIP_TRY(hipMalloc(&h->d_ds_wall, nwall * sizeof(double)));
+    if (wall_b) HIP_TRY(hipMemcpyAsync(h->d_ds_wall, wall_b, nwall * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    const double *wall = wall_b ? h->d_ds_wall : nullptr;
+    // the state as it is NOW, taken the way rbc_get_flowstats takes it; not recorded by the profiling events
+    if (h->s3) {
+        P.env_stride = RBC_S3(h, env_stride3d, h);
+        P.ou = h->ncell; P.ov = 2 * h->ncell; P.ow = 3 * h->ncell;
+        const void *st = RBC_S3(h, dev_fields3d, h);
+        if (h->s3_f32) HIP_TRY((rbcds::launch_dissipation<float, true>(P, static_cast<const float *>(st), wall, h->B, h->d_ds_part, h->d_ds_cells, h->d_ds_faces, h->d_ds_tot, h->stream)));
+        else HIP_TRY((rbcds::launch_dissipation<double, true>(P, static_cast<const double *>(st), wall, h->B, h->d_ds_part, h->d_ds_cells, h->d_ds_faces, h->d_ds_tot, h->stream)));
+    } else {
+        P.env_stride = h->env_stride;
+        P.ou = h->ncell; P.ov = 0; P.ow = 2 * h->ncell;
+        HIP_TRY((rbcds::launch_dissipation<double, false>(P, h->d_fields, wall, h->B, h->d_ds_part, h->d_ds_cells, h->d_ds_faces, h->d_ds_tot, h->stream)));
+    }
+    if (cells) HIP_TRY(hipMemcpyAsync(cells, h->d_ds_cells, ncells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (faces) HIP_TRY(hipMemcpyAsync(faces, h->d_ds_faces, nfaces * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (tot) HIP_TRY(hipMemcpyAsync(tot, h->d_ds_tot, ntot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (cells || faces || tot) HIP_TRY(hipStreamSynchronize(h->stream));
+    return RBC_OK;
+}
+
+void *rbc_dev_dissipation(rbc_handle *h, int which)
+{
+    if (!h) return nullptr;
+    if (which < 0 || which > 2) { fail(RBC_ERR_INVALID, "rbc_dev_dissipation: which must be 0 (cells), 1 (faces) or 2 (tot)"); return nullptr; }
+    return which == 0 ? h->d_ds_cells : which == 1 ? h->d_ds_faces : h->d_ds_tot;
 }
 
 void *rbc_host_alloc(size_t bytes)

@@ -106,6 +106,8 @@ SYMBOLS = {
     "rbc_dev_flowstats": (_vp, [_vp, C.c_int]),
     "rbc_get_spectra": (C.c_int, [_vp, _dp, _dp]),
     "rbc_dev_spectra": (_vp, [_vp, C.c_int]),
+    "rbc_get_dissipation": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
+    "rbc_dev_dissipation": (_vp, [_vp, C.c_int]),
 }
 
 _lib = None
@@ -268,7 +270,8 @@ def torch_stream_handle(stream):
 
 
 class _FlowStats:
-    """get_flowstats / flowstats_views of NativeSim and NativeSim3D (include/rbc_hip.h rbc_get_flowstats)"""
+    """get_flowstats / flowstats_views and get_dissipation / dissipation_views of NativeSim and NativeSim3D (include/rbc_hip.h
+    rbc_get_flowstats, rbc_get_dissipation)"""
 
     def get_flowstats(self):
         """(prof, ext), float64: prof (B, 6, nz) = per-level means of b, u^2, v^2, w^2, b w, b^2; ext (B, 5) = max |u|, max |v|,
@@ -287,6 +290,42 @@ class _FlowStats:
         dev = f"cuda:{self.cfg.device}"
         return {"profiles": torch.as_tensor(DeviceArray(self.lib.rbc_dev_flowstats(self.h, 0), (self.B, 6, self.nz), "<f8", self), device=dev),
                 "extrema": torch.as_tensor(DeviceArray(self.lib.rbc_dev_flowstats(self.h, 1), (self.B, 5), "<f8", self), device=dev)}
+
+    def _dissipation_shapes(self):
+        return (self.B, 4, self.nz), (self.B, 5, self.nz + 1), (self.B, 4)
+
+    def get_dissipation(self, wall_b=None):
+        """(cells, faces, tot), float64: level means of the squared difference quotients of b, u, v, w at their staggered places --
+        cells (B, 4, nz), faces (B, 5, nz + 1) -- and their volume means tot (B, 4), computed on the device from the solver's own
+        state (include/rbc_hip.h rbc_get_dissipation).  wall_b: the bottom plate's temperature (B, ny, nx) ((B, nx) for a 2D sim);
+        None = the uniform plate min_b + delta_b"""
+        wp = None
+        if wall_b is not None:
+            want = (self.B, getattr(self, "ny", 1), self.nx)
+            wall_b = np.ascontiguousarray(wall_b, np.float64)
+            if wall_b.shape != want and not (want[1] == 1 and wall_b.shape == (self.B, self.nx)):
+                raise ValueError(f"get_dissipation: wall_b must have shape {want} (batch, y, x), got {wall_b.shape}")
+            wp = _ptr(wall_b, _dp)
+        cells, faces, tot = (np.empty(s) for s in self._dissipation_shapes())
+        self._check(self.lib.rbc_get_dissipation(self.h, wp, _ptr(cells, _dp), _ptr(faces, _dp), _ptr(tot, _dp)))
+        return cells, faces, tot
+
+    def dissipation_views(self):
+        """the same numbers for the uniform plate as zero-copy torch tensors {"cells", "faces", "tot"} over the library's device
+        buffers, under the rules of flowstats_views: queued on the sim's stream, nothing copied or waited for, rewritten by the next call"""
+        import torch
+        from .vector import DeviceArray
+        self._check(self.lib.rbc_get_dissipation(self.h, None, None, None, None))
+        dev = f"cuda:{self.cfg.device}"
+        return {name: torch.as_tensor(DeviceArray(self.lib.rbc_dev_dissipation(self.h, which), shape, "<f8", self), device=dev)
+                for which, (name, shape) in enumerate(zip(("cells", "faces", "tot"), self._dissipation_shapes()))}
+
+    def nu_kappa(self):
+        """(nu, kappa), (B,) each: the viscosity and the diffusivity the solver uses for every env, sqrt(Pr / Ra) and 1 / sqrt(Pr Ra)
+        with the Rayleigh numbers of the last set_rayleigh (rbc_api.hip rbc_set_rayleigh)"""
+        ra = getattr(self, "_ra", None)
+        ra = np.full(self.B, self.cfg.ra) if ra is None else ra
+        return np.sqrt(self.cfg.pr / ra), 1.0 / np.sqrt(self.cfg.pr * ra)
 
 
 class _Spectra:
@@ -382,6 +421,7 @@ class NativeSim(_FlowStats, _Spectra):
     def set_rayleigh(self, ra):
         r = np.ascontiguousarray(np.broadcast_to(np.asarray(ra, np.float64), (self.B,)))
         self._check(self.lib.rbc_set_rayleigh(self.h, _ptr(r, _dp)))
+        self._ra = r.copy()                                  # nu_kappa()
 
     def set_obs_normalization(self, min_vals=None, max_vals=None, maxval=1.0, clip=False):
         """RBCNormalizeObservation fused into the kernel's observation write; None switches it off."""
@@ -558,6 +598,7 @@ class NativeSim3D(_FlowStats, _Spectra):
     def set_rayleigh(self, ra):
         r = np.ascontiguousarray(np.broadcast_to(np.asarray(ra, np.float64), (self.B,)))
         self._check(self.lib.rbc_set_rayleigh(self.h, _ptr(r, _dp)))
+        self._ra = r.copy()                                  # nu_kappa()
 
     def set_obs_normalization(self, min_vals=None, max_vals=None, maxval=1.0, clip=False):
         """RBCNormalizeObservation fused into the output kernel's float32 state write (channels b, u, v, w); None switches it off."""

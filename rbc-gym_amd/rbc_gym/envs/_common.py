@@ -142,6 +142,29 @@ def power_spectra_dict(sim, single=False):
     return {"x": px, "y": py, "kx": kx, "ky": ky, "channels": SPECTRA_CHANNELS}
 
 
+def dissipation_rates_dict(sim, wall_b=None, single=False):
+    """`sim.get_dissipation(wall_b)` under names (include/rbc_hip.h rbc_get_dissipation; wall_b: the bottom plate's temperature,
+    None = the uniform plate): "cells" (B, 4, nz) and "faces" (B, 5, nz + 1), the level means of the squared difference quotients,
+    and per env, with the viscosity nu = sqrt(Pr / Ra) and the diffusivity kappa = 1 / sqrt(Pr Ra) the solver uses for that env,
+      "thermal_dissipation" = kappa <|grad b|^2>,  "kinetic_dissipation" = nu <d_j u_i d_j u_i>,  "enstrophy" = <|curl u|^2>,
+      "nusselt_thermal" = <|grad b|^2> lz^2 / delta_b^2,  "nusselt_viscous" = 1 + kinetic_dissipation lz / (kappa delta_b).
+    The last two follow from the volume means of b times its equation (kappa <|grad b|^2> = the plates' flux times delta_b / lz) and
+    of u times its equation (the buoyancy term of the w equation is b itself: eps_u = <w b> = kappa delta_b / lz (Nu - 1)); they
+    equal the Nusselt number only for uniform plates in a statistically steady state -- the Nusselt number in units of the conductive
+    flux kappa delta_b / lz, that is 1 + (Nu_info - 1) lz / delta_b for the 3D envs' info["nusselt"] = 1 + <w b'> / kappa (the reference's
+    normalisation, rbc_sim3D_api.jl:134-159).  single: one env, without the batch axis"""
+    cells, faces, tot = sim.get_dissipation(wall_b)
+    nu, kappa = sim.nu_kappa()
+    lz, delta_b = sim.cfg.lz, sim.cfg.delta_b
+    eps_u = nu * (tot[:, 1] + tot[:, 2])
+    out = {"cells": cells, "faces": faces, "thermal_dissipation": kappa * tot[:, 0], "kinetic_dissipation": eps_u,
+           "enstrophy": tot[:, 2] - 2.0 * tot[:, 3], "nusselt_thermal": tot[:, 0] * lz ** 2 / delta_b ** 2,
+           "nusselt_viscous": 1.0 + eps_u * lz / (kappa * delta_b)}
+    if single:
+        out = {k: (v[0] if k in ("cells", "faces") else float(v[0])) for k, v in out.items()}
+    return out
+
+
 class NativeEnvBase(gym.Env):
     """One env = a batch-of-one simulation handle.  Subclasses provide `_fields` (dataset names of a checkpoint
     episode), `_observe()`, `_info()` and `_reward()`."""
@@ -212,6 +235,11 @@ class NativeEnvBase(gym.Env):
     def power_spectra(self):
         """Horizontal power and co-spectra of the current state, level by level, computed on the device: see power_spectra_dict"""
         return power_spectra_dict(self.sim, single=True)
+
+    def dissipation_rates(self, wall_b=None):
+        """Dissipation rates, enstrophy and the dissipation-based Nusselt numbers of the current state, computed on the device:
+        see dissipation_rates_dict (wall_b: (ny, nx), 2D (nx,); None = the uniform plate)"""
+        return dissipation_rates_dict(self.sim, None if wall_b is None else np.asarray(wall_b, np.float64)[None], single=True)
 
     # ---- teardown --------------------------------------------------------------------------------
     def close(self):

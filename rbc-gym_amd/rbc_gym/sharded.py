@@ -141,6 +141,17 @@ class ShardedSim:
     def get_flowstats(self):
         return self._cat(self._all(lambda r, sim: tuple(sim.get_flowstats())))
 
+    def get_dissipation(self, wall_b=None):
+        w = self._split(wall_b, np.float64)
+        return self._cat(self._all(lambda r, sim: tuple(sim.get_dissipation(w[r]))))
+
+    def nu_kappa(self):
+        return self._cat(self._all(lambda r, sim: tuple(sim.nu_kappa())))
+
+    @property
+    def cfg(self):
+        return self.sims[0].cfg
+
     def get_spectra(self):
         parts = self._all(lambda r, sim: tuple(sim.get_spectra()))
         if parts[0][1] is None:                              # 2D sims have no y spectra

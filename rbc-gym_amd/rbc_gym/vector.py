@@ -16,7 +16,7 @@ from ._gym import gym
 from . import _native
 from .checkpoint import read_checkpoint
 from .sharded import ShardedSim
-from .envs._common import check_checkpoint_grid, checkpoint_index, flow_statistics_dict, power_spectra_dict
+from .envs._common import check_checkpoint_grid, checkpoint_index, dissipation_rates_dict, flow_statistics_dict, power_spectra_dict
 from .envs.rbc2D import build_spaces, sim_kwargs
 
 
@@ -126,6 +126,11 @@ class _BatchedEnv(gym.vector.VectorEnv):
         """Horizontal power and co-spectra of every env's current state, level by level, computed on the device from the solver's own
         state; with devices=[...] the shards' results in env order.  See power_spectra_dict."""
         return power_spectra_dict(self.sim)
+
+    def dissipation_rates(self, wall_b=None):
+        """Dissipation rates, enstrophy and the dissipation-based Nusselt numbers of every env's current state, computed on the device
+        from the solver's own state; with devices=[...] the shards' results in env order.  See dissipation_rates_dict."""
+        return dissipation_rates_dict(self.sim, wall_b)
 
     def _pooled(self, shape, mode):
         """destination for a large host output: a page-locked array nobody else references (None: let the getter allocate)"""

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Register / scratch / LDS budget of every kernel in librbc_hip.so, read from the metadata of its gfx950 code objects (one per translation unit).
 
-    python scripts/kernel_resources.py [path/to/librbc_hip.so] [substring ...]
+    python scripts/kernel_resources.py [path/to/librbc_hip.so] [substring | group ...]
+
+A group names the kernels of one header (GROUPS): `flowstats`, `spectra`, `dissipation`.
 
 The .so carries a clang offload bundle in its .hip_fatbin section; llvm-objcopy dumps it, clang-offload-bundler takes the
 hipv4-amdgcn-amd-amdhsa--gfx950 entry out, llvm-readelf --notes prints the AMDGPU metadata (one YAML map per kernel).  All
@@ -18,6 +20,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = os.environ.get("ROCM_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
+GROUPS = {"flowstats": ("rbcfs::",), "spectra": ("rbcsp::",), "dissipation": ("rbcds::",)}     # a header's kernels by their namespace
 KEYS = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
         "group_segment_fixed_size", "max_flat_workgroup_size")
 
@@ -79,7 +82,7 @@ def kernel_resources(lib=None):
 
 if __name__ == "__main__":
     lib = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].endswith(".so") else None
-    pats = [a for a in sys.argv[1:] if not a.endswith(".so")]
+    pats = [p for a in sys.argv[1:] if not a.endswith(".so") for p in GROUPS.get(a, ()) + (a,)]
     res = kernel_resources(lib)
     print(f"{'kernel':78s} vgpr agpr sgpr vspill sspill scratch   lds")
     for name, r in res.items():
