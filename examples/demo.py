@@ -6,8 +6,9 @@
     python examples/demo.py vector [envs] [steps]   gym.make_vec -> ONE device-batched env (6 or 6000 envs alike)
     python examples/demo.py wrapped [steps]         observation / reward normalisation + reward shaping wrappers
     python examples/demo.py checkpoint [file] [steps]   episodes from converged states (generated on the GPU if absent)
-    python examples/demo.py three-d [time] [f32] [recorded]   the 3D env (f32: the float32 instantiation of the 3D kernels; recorded: the
-                                                    solver-step count of the reference's recorded flowstats series)
+    python examples/demo.py three-d [time] [f32] [recorded] [large]   the 3D env (f32: the float32 instantiation of the 3D kernels; recorded: the
+                                                    solver-step count of the reference's recorded flowstats series, INTEGRATION.md section 5;
+                                                    large: a 128 x 128 x 64 grid on the chunked pressure projection)
     python examples/demo.py flowstats [envs] [steps]   the loop of the reference's experiments/flowstats/flowstats_ra.py: Nu and max |u|, |v|, |w|
                                                     after every env-step, from the device's statistics kernel instead of whole fields
     python examples/demo.py spectra [envs] [steps]     horizontal power spectra of the 3D envs from the device's spectra kernels: mid-level
@@ -107,9 +108,11 @@ def checkpoint(args):
 def three_d(args):
     precision = "f32" if "f32" in args else "f64"
     clock = "recorded" if "recorded" in args else "documented"
-    args = [a for a in args if a not in ("f32", "recorded")]
+    # a (y, z) plane of 128 x 64 values is beyond the one-plane pencil solve: projection="chunked" (dz = 2/64 needs the shorter solver step)
+    large = dict(state_shape=(64, 128, 128), projection="chunked", dt_solver=0.005) if "large" in args else {}
+    args = [a for a in args if a not in ("f32", "recorded", "large")]
     env = gym.make(ENV3D, rayleigh_number=2500, heater_duration=0.25, episode_length=_int(args, 0, 50), precision=precision,
-                   reference_clock=clock)
+                   reference_clock=clock, **large)
     obs, _ = rollout(env, 10**9, zero_action, keys=("nusselt",))
     print("observation", obs.shape)
     env.close()

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RBC_ABI_VERSION 3
+#define RBC_ABI_VERSION 4
 
 /* status codes */
 enum {
@@ -56,7 +56,9 @@ typedef struct rbc_config {
                                 dim=3: every direction >= 8.  Horizontal slabs that fit one workgroup's LDS (nx*ny <=
                                 ~5000 in float64, ~10000 in float32) take the slab projection, larger ones the row /
                                 pencil projection, whose bound is one (y, z) plane in LDS:
-                                ny*nz <= ~5000 (float64), ~10000 (float32); beyond it rbc_create returns RBC_ERR_INVALID.
+                                ny*nz <= ~5000 (float64), ~10000 (float32); beyond it rbc_create returns RBC_ERR_INVALID unless
+                                `projection` below asks for the chunked y-z solve, whose bound is one line of y (128 x 128 x 64,
+                                256 x 256 x 128, ... in either precision).  Every handle: batch * nx * ny * (nz + 1) < 2^31.
                                 Tendencies: LDS tiles over full rows of x up to nx = 64, x- and y-tiled LDS tiles on wider grids
                                 with nx % 32 == 0, ny % 8 == 0, nz % 4 == 0, the z-marching kernels otherwise
                                 (rbc_debug_tendency_path tells which)                                                          */
@@ -93,10 +95,20 @@ typedef struct rbc_config {
                                 t and step reported by rbc_get_info advance as documented.  Per env: a masked reset
                                 restores the full first interval for the envs it resets, whatever the others are doing.
                                 Needs dt_control > dt_solver.  dim = 2 and 3, every precision and path.                */
+    int32_t projection;      /* dim = 3, which pressure projection the handle runs (ABI 4; ignored for dim = 2).
+                                RBC_PROJECTION_AUTO (0, default): the slab kernels where a horizontal slab fits the LDS, the row /
+                                pencil projection otherwise, refused beyond its (y, z) plane bound.
+                                RBC_PROJECTION_PENCIL (1): the row / pencil projection on any 3D grid (what RBC_3D_PENCIL=1 forces).
+                                RBC_PROJECTION_CHUNKED (2, or RBC_3D_PENCIL=2 in the environment): rows along x as in the pencil
+                                projection, and the (y, z) plane walked in chunks of levels through memory instead of held in LDS
+                                (DESIGN.md section 3b): bound ny <= ~2500 (float64), ~5100 (float32).  The chunk height follows from
+                                the grid and the precision alone; RBC_PENCIL_CHUNK=<levels>, read by rbc_create, forces it.
+                                Any other value: RBC_ERR_INVALID.                                                       */
 } rbc_config;
 
 enum { RBC_PRECISION_F64 = 0, RBC_PRECISION_F32 = 1 };
 enum { RBC_CLOCK_DOCUMENTED = 0, RBC_CLOCK_RECORDED = 1 };
+enum { RBC_PROJECTION_AUTO = 0, RBC_PROJECTION_PENCIL = 1, RBC_PROJECTION_CHUNKED = 2 };
 
 typedef struct rbc_handle rbc_handle;
 
@@ -322,6 +334,9 @@ int  rbc_debug_launch_plan(rbc_handle *h, int groups[2]);
    RBC_TILE_SHAPE=16x16|16x8|16x4|8x8 forces a full-row shape, RBC_TILE_X=0 keeps wide grids on the z-marching kernels, RBC_TILE_X=1
    takes the x-tiled kernel on every 3D grid with nx % 32 == 0, ny % 8 == 0, nz % 4 == 0 (nx <= 64 included).                      */
 int  rbc_debug_tendency_path(rbc_handle *h, int *path);
+/* which pressure projection the handle's stage plan launches: *path = 0 slab kernels, 1 row / pencil projection with the one-plane
+   y-z solve, 2 with the chunked y-z solve; -1 for a handle on the LDS-resident 2D kernel or on the streaming 2D path.        */
+int  rbc_debug_projection_path(rbc_handle *h, int *path);
 /* diagnostic builds only (-DRBC_STAMPS=1): per-phase shader-clock cycles of the last launch,
    out[B][64]; returns RBC_ERR_INVALID in the shipped build                                 */
 int  rbc_debug_stamps(rbc_handle *h, unsigned long long *out);

@@ -37,6 +37,8 @@ struct rbc3_state {
     int fft_threads = 256;             // slab-FFT workgroup: one round of work items for the larger of nx, ny (8 items per line)
     int pencil = 0;                    // 3D: rows of y per workgroup of the row / pencil projection (k3p_*), 0 = the slab kernels
     size_t pencil_x_lds = 0, pencil_yz_lds = 0;
+    int chunk = 0;                     // 3D: levels per chunk of k3p_yz_chunked in place of k3p_yz_solve, 0 = the one-plane solve
+    int chunk_prefetch = 1;            // ... with the next chunk fetched into registers one chunk ahead (RBC_PENCIL_PREFETCH=0: the A/B partner)
     real *tab_pencil = nullptr;        // the pivot table in the order [m][k][ky], m = 0 .. nx/2 (k3p_yz_solve reads a plane of it contiguously)
     int march = 0;                     // 3D: 2 = k3_ifft_march (inverse FFT + the whole correction), 0 = k3_ifft_pair + k3_correct_w
     double tff = 1.0;
@@ -110,6 +112,12 @@ constexpr int TW3 = std::is_same<real, float>::value ? RBC_F32_TILE_WAVES : 3;
 // waves, which spilled -- so two (two workgroups per CU, the waves of one 32 x 16 workgroup); float32 fits three
 constexpr int TWX8 = std::is_same<real, float>::value ? 3 : 2;
 
+// complex values per thread that k3p_yz_chunked fetches one chunk ahead: 16 VGPRs in either precision, half of a chunk of the 64 KB
+// budget (2 KC (ny|1) values for both line buffers, 256 threads); the rest of a chunk is loaded when its turn comes.  A whole chunk
+// ahead (32 VGPRs) took the kernel to 166 (float64) / 131 (float32) VGPRs, over the 128 that tests/test_kernel_resources_chunk.py pins:
+// the registers stay live across the DFT-16 of a 128-value line, which needs 64 of its own in float64
+constexpr int CHUNK_PF = std::is_same<real, float>::value ? 8 : 4;
+
 inline rbc3_state *S3(const rbc_handle *h) { return static_cast<rbc3_state *>(h->s3); }
 
 // true if a kernel on `b` can run while one is running on `a`, i.e. the two streams do not share a hardware queue: `a` is held
@@ -174,6 +182,10 @@ int create3d(rbc_handle *h)
     g.nx = c.nx; g.ny = ny; g.nz = c.nz;
     g.nc = c.nx * ny * c.nz; g.nw = c.nx * ny * (c.nz + 1);
     g.env_stride = (size_t)3 * g.nc + g.nw;
+    // the cell-per-thread kernels (reset, IC, output, k3_correct_w, ...) index the batch's cells with an int, and the tile kernels address
+    // an env through a buffer resource with 32-bit byte offsets
+    if ((size_t)c.nx * ny * (c.nz + 1) * (size_t)h->B > (size_t)INT32_MAX || g.env_stride * sizeof(real) > (size_t)INT32_MAX)
+        return fail(RBC_ERR_INVALID, "grid too large: batch * nx * ny * (nz + 1) must stay below 2^31 cells and one env's state below 2 GiB");
     g.lx = c.lx; g.ly = ly; g.lz = c.lz;
     g.dx = c.lx / c.nx; g.dy = ly / ny; g.dz = c.lz / c.nz;
     g.rdx = 1.0 / g.dx; g.rdy = 1.0 / g.dy; g.rdz = 1.0 / g.dz;
@@ -243,12 +255,36 @@ int create3d(rbc_handle *h)
     // 3D grids whose slab does not fit the slab-FFT workgroup take the row / pencil projection (RBC_3D_PENCIL=1 forces it on any 3D
     // grid, the A/B partner of the slab kernels); its own bound is the (env, m) plane of k3p_yz_solve: two copies of nz lines of ny | 1
     // complex values plus the y twiddles.  Rows per workgroup of the two x kernels: 32, fewer where the rows are long.
+    // rbc_config.projection: RBC_PROJECTION_PENCIL is what RBC_3D_PENCIL=1 forces; RBC_PROJECTION_CHUNKED (RBC_3D_PENCIL=2) keeps the two
+    // x-row kernels and walks the (y, z) plane in chunks of KC levels (k3p_yz_chunked), whose bound is one line of y instead of the plane.
+    // KC depends on the grid and the precision alone, never on the batch (an env's result must not depend on its batch or group): the
+    // largest whose LDS stays within 64 KB (two workgroups per CU), one level up to the LDS ceiling where that does not fit.
+    // RBC_PENCIL_CHUNK=<levels> forces it (tests and A/B runs: small grids would all be one chunk).  RBC_PROJECTION_AUTO never takes the
+    // chunked solve yet: tests/test_gpu_pencil3d.py pins the refusal below.
     const char *pe = std::getenv("RBC_3D_PENCIL");
-    if (!h->stream2d && (s->fft_lds > (size_t)RBC_LDS_CEILING || (pe && pe[0] == '1'))) {
-        s->pencil_yz_lds = ((size_t)2 * c.nz * K3::slab_row(ny) + ny) * sizeof(real2);
-        if (s->pencil_yz_lds > (size_t)RBC_LDS_CEILING)
-            return fail(RBC_ERR_INVALID, std::string("3D grid too large for the pencil projection: one (y, z) plane must fit the LDS, ny*nz <= ~") +
-                                         (std::is_same<real, double>::value ? "5000 (float64)" : "10000 (float32)"));
+    const int proj = c.projection != RBC_PROJECTION_AUTO ? c.projection : (pe && pe[0] == '2') ? RBC_PROJECTION_CHUNKED : (pe && pe[0] == '1') ? RBC_PROJECTION_PENCIL : RBC_PROJECTION_AUTO;
+    if (!h->stream2d && (s->fft_lds > (size_t)RBC_LDS_CEILING || proj != RBC_PROJECTION_AUTO)) {
+        if (proj == RBC_PROJECTION_CHUNKED) {
+            auto yz_lds = [&](int kc) { return ((size_t)2 * kc * K3::slab_row(ny) + 2 * (size_t)ny) * sizeof(real2); };
+            int kc = 1;
+            while (kc < c.nz && yz_lds(kc + 1) <= 64 * 1024) ++kc;
+            if (const char *e = std::getenv("RBC_PENCIL_CHUNK")) {
+                kc = std::atoi(e);
+                if (kc < 1) return fail(RBC_ERR_INVALID, "RBC_PENCIL_CHUNK must be a number of levels >= 1");
+                if (kc > c.nz) kc = c.nz;
+            }
+            if (yz_lds(kc) > (size_t)RBC_LDS_CEILING)
+                return fail(RBC_ERR_INVALID, std::string("3D grid too large for the chunked pencil projection: ") + std::to_string(kc) + " level(s) of ny values do not fit the LDS; at one level per chunk ny <= ~" +
+                                             (std::is_same<real, double>::value ? "2500 (float64)" : "5100 (float32)"));
+            s->chunk = kc; s->pencil_yz_lds = yz_lds(kc);
+            if (const char *e = std::getenv("RBC_PENCIL_PREFETCH")) s->chunk_prefetch = (e[0] != '0');
+        } else {
+            s->pencil_yz_lds = ((size_t)2 * c.nz * K3::slab_row(ny) + ny) * sizeof(real2);
+            if (s->pencil_yz_lds > (size_t)RBC_LDS_CEILING)
+                return fail(RBC_ERR_INVALID, std::string("3D grid too large for the pencil projection: one (y, z) plane must fit the LDS, ny*nz <= ~") +
+                                             (std::is_same<real, double>::value ? "5000 (float64)" : "10000 (float32)") +
+                                             "; projection = RBC_PROJECTION_CHUNKED (RBC_3D_PENCIL=2) walks the plane in chunks instead");
+        }
         int R = 32;
         auto x_lds = [&](int r) { return ((size_t)(r + 2) * K3::slab_row(c.nx) + c.nx) * sizeof(real2); };      // k3p_ifftx_correct's, the larger of the two
         while (R > 2 && x_lds(R) > 64 * 1024) R /= 2;
@@ -256,6 +292,7 @@ int create3d(rbc_handle *h)
         s->pencil = R; s->pencil_x_lds = x_lds(R);
         RBC_LDS_ATTR(K3::k3p_div_fftx);
         RBC_LDS_ATTR(K3::k3p_yz_solve);
+        RBC_LDS_ATTR(K3::k3p_yz_chunked<CHUNK_PF>);
         RBC_LDS_ATTR(K3::k3p_ifftx_correct);
     } else
     if (s->fft_lds > 160 * 1024) return fail(RBC_ERR_INVALID, "3D horizontal slab too large for the LDS FFT (nx*ny <= ~5000)");
@@ -430,7 +467,8 @@ int project3d(rbc_handle *h, const rbc3_grp &q, int which, double dts, const uin
         real2 *spec = s->spec + (size_t)q.e0 * (g.nx / 2 + 1) * g.ny * g.nz;
         const dim3 gx((unsigned)((size_t)B * g.nz * ((g.ny + s->pencil - 1) / s->pencil)));
         hipLaunchKernelGGL(K3::k3p_div_fftx, gx, dim3(256), s->pencil_x_lds, q.st, g, s->plan, buf, spec, dts, s->pencil);
-        hipLaunchKernelGGL(K3::k3p_yz_solve, dim3((unsigned)(B * (g.nx / 2 + 1))), dim3(256), s->pencil_yz_lds, q.st, g, s->plan, spec, s->tab_pencil);
+        if (s->chunk) hipLaunchKernelGGL(K3::k3p_yz_chunked<CHUNK_PF>, dim3((unsigned)(B * (g.nx / 2 + 1))), dim3(256), s->pencil_yz_lds, q.st, g, s->plan, spec, s->tab_pencil, s->chunk, s->chunk_prefetch);
+        else hipLaunchKernelGGL(K3::k3p_yz_solve, dim3((unsigned)(B * (g.nx / 2 + 1))), dim3(256), s->pencil_yz_lds, q.st, g, s->plan, spec, s->tab_pencil);
         hipLaunchKernelGGL(K3::k3p_ifftx_correct, gx, dim3(256), s->pencil_x_lds, q.st, g, s->plan, spec, phi, buf, dts, mk, s->pencil);
         hipLaunchKernelGGL(K3::k3_correct_w, grid_for((size_t)B * (g.nc - pln), 256), dim3(256), 0, q.st, g, buf, phi, dts, B, mk);
         HIP3(hipGetLastError());
@@ -596,6 +634,14 @@ int tend_shape3d(const rbc_handle *h, int Bn)
         }
     }
     return shape;
+}
+
+// rbc_debug_projection_path: 0 slab kernels, 1 row / pencil with the one-plane solve, 2 with the chunked solve (what project3d launches)
+int projection_path3d(const rbc_handle *h)
+{
+    const rbc3_state *s = S3(h);
+    if (h->stream2d) return -1;
+    return s->pencil ? (s->chunk ? 2 : 1) : 0;
 }
 
 // rbc_debug_tendency_path: 0 cell-per-thread, 1 z-marching, 2 full-row tiles, 3 flat (streaming 2D), 4 x-tiled

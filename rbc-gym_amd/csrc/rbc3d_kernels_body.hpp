@@ -1716,6 +1716,121 @@ __global__ RBC_PENCIL_TARGET void __launch_bounds__(256) k3p_yz_solve(Geo3 g, Ff
     for (int idx = threadIdx.x; idx < nz * ny; idx += blockDim.x) { const int k = idx / ny; io[idx] = Q[idx + k * (nyp - ny)]; }
 }
 
+// Kernel B for planes that do not fit the LDS: the same (env, m) plane, walked in chunks of KC levels, so that the workgroup never
+// holds more than KC lines.  The plane makes a round trip through `spec`, written and re-read by this workgroup alone:
+//   upward, chunk by chunk from the bottom:  load KC lines, y transform of all of them at once, forward elimination of k3p_yz_solve
+//       continued from the carry y of the chunk below, eliminated lines back to `spec` in place;
+//   downward, from the top:                  reload (the top chunk is still in LDS), back-substitution continued from the carry x of
+//       the chunk above, inverse y transform, result to `spec` in place.
+// One thread per (ky, real | imaginary part) runs the recurrence, with k3p_yz_solve's operand order and its pivots fetched BK levels
+// ahead; its carry lives in LDS (2 ny reals: a thread may own several columns).  Data movement: with `prefetch`, the first PF values
+// per thread of the NEXT chunk are fetched into registers before this chunk is transformed and solved (the one-ahead scheme of the tile
+// kernels: the loads fly under the transform and the recurrence); what a chunk holds beyond PF * 256 values is loaded when its turn
+// comes.  pencil_barrier() between a chunk's stores and every later load of them; no atomics, nothing passes between workgroups.
+// grid = B * (nx/2 + 1); LDS: 2 * KC * (ny|1) + 2 * ny complex values.
+template <int PF>
+__device__ __forceinline__ RBC_PENCIL_TARGET void chunk_fetch(real (&nr)[PF], real (&ni)[PF], const real2 *src, int n)
+{
+#pragma unroll
+    for (int q = 0; q < PF; ++q) { const int idx = threadIdx.x + q * 256; if (idx < n) { const real2 v = src[idx]; nr[q] = v.x; ni[q] = v.y; } }
+}
+
+// n contiguous values (lines of ny) -> the padded lines of S: the first PF per thread from the registers (or from src where nothing
+// was prefetched), the rest from src
+template <int PF>
+__device__ __forceinline__ RBC_PENCIL_TARGET void chunk_put(real2 *S, const real (&nr)[PF], const real (&ni)[PF], const real2 *src, int n, int ny, int nyp, bool fetched)
+{
+#pragma unroll
+    for (int q = 0; q < PF; ++q) {
+        const int idx = threadIdx.x + q * 256;
+        if (idx < n) S[idx + (idx / ny) * (nyp - ny)] = fetched ? make_real2(nr[q], ni[q]) : src[idx];
+    }
+    for (int idx = threadIdx.x + PF * 256; idx < n; idx += 256) S[idx + (idx / ny) * (nyp - ny)] = src[idx];
+}
+
+__device__ __forceinline__ RBC_PENCIL_TARGET void chunk_store(real2 *dst, const real2 *Q, int n, int ny, int nyp)
+{
+    for (int idx = threadIdx.x; idx < n; idx += 256) dst[idx] = Q[idx + (idx / ny) * (nyp - ny)];
+}
+
+template <int PF>
+__global__ RBC_PENCIL_TARGET void __launch_bounds__(256) k3p_yz_chunked(Geo3 g, FftPlan pl, real2 *spec, const real *tabp, int KC, int prefetch)
+{
+    extern __shared__ __attribute__((aligned(16))) real2 sm[];
+    const int nx = g.nx, ny = g.ny, nz = g.nz, nm = nx / 2 + 1, nyp = slab_row(ny);
+    const int env = blockIdx.x / nm, m = blockIdx.x - env * nm;
+    const int nch = (nz + KC - 1) / KC;
+    real2 *S = sm, *D = sm + KC * nyp, *twy = sm + 2 * KC * nyp;
+    real *carry = reinterpret_cast<real *>(twy + ny);             // [2 ny]: y of the level below on the way up, x of the level above on the way down
+    for (int t = threadIdx.x; t < ny; t += 256) twy[t] = pl.tw[nx + t];
+    for (int t = threadIdx.x; t < 2 * ny; t += 256) carry[t] = real(0.0);
+    real2 *io = spec + ((size_t)env * nm + m) * nz * ny;
+    const real *tm = tabp + (size_t)m * nz * ny;
+    const real o = g.rdz * g.rdz;
+    constexpr int BK = 8;
+    const bool pf = prefetch != 0;
+    real nr[PF], ni[PF];
+    if (pf) chunk_fetch<PF>(nr, ni, io, (KC < nz ? KC : nz) * ny);
+    real2 *P = S;
+    for (int c = 0; c < nch; ++c) {                               // upward: transform and eliminate
+        const int k0 = c * KC, kc = (nz - k0 < KC) ? nz - k0 : KC;
+        chunk_put<PF>(S, nr, ni, io + (size_t)k0 * ny, kc * ny, ny, nyp, pf);
+        if (pf && c + 1 < nch) chunk_fetch<PF>(nr, ni, io + (size_t)(k0 + KC) * ny, ((nz - k0 - KC < KC) ? nz - k0 - KC : KC) * ny);
+        pencil_barrier();
+        P = pencil_lines(S, D, kc, ny, pl.ny1, pl.ny2, nyp, twy, -1);
+        const real *tc = tm + (size_t)k0 * ny;
+        for (int t = threadIdx.x; t < 2 * ny; t += 256) {
+            const int ky = t >> 1;
+            real *col = reinterpret_cast<real *>(P) + t;           // real (t even) or imaginary (t odd) part of column ky, level stride 2 nyp
+            real y = carry[t];
+            int k = 0;
+            for (; k + BK <= kc; k += BK) {
+                real inv[BK];
+#pragma unroll
+                for (int q = 0; q < BK; ++q) inv[q] = tc[(k + q) * ny + ky];
+#pragma unroll
+                for (int q = 0; q < BK; ++q) { y = col[2 * (k + q) * nyp] * inv[q] - (inv[q] * o) * y; col[2 * (k + q) * nyp] = y; }
+            }
+            for (; k < kc; ++k) { const real inv = tc[k * ny + ky]; y = col[2 * k * nyp] * inv - (inv * o) * y; col[2 * k * nyp] = y; }
+            carry[t] = (c + 1 < nch) ? y : real(0.0);             // (the downward pass starts from x = 0 above the top level)
+        }
+        if (c + 1 < nch) {                                        // the top chunk stays in LDS for the downward pass
+            pencil_barrier();
+            chunk_store(io + (size_t)k0 * ny, P, kc * ny, ny, nyp);
+            pencil_barrier();                                     // S is overwritten by the next chunk
+        }
+    }
+    for (int c = nch - 1; c >= 0; --c) {                          // downward: back-substitute and transform back
+        const int k0 = c * KC, kc = (nz - k0 < KC) ? nz - k0 : KC;
+        if (c + 1 < nch) {
+            chunk_put<PF>(S, nr, ni, io + (size_t)k0 * ny, kc * ny, ny, nyp, pf);
+            P = S;
+        }
+        if (pf && c > 0) chunk_fetch<PF>(nr, ni, io + (size_t)(k0 - KC) * ny, KC * ny);
+        if (c + 1 < nch) pencil_barrier();
+        const real *tc = tm + (size_t)k0 * ny;
+        for (int t = threadIdx.x; t < 2 * ny; t += 256) {
+            const int ky = t >> 1;
+            real *col = reinterpret_cast<real *>(P) + t;
+            real x = carry[t];
+            int k = kc - 1;
+            for (; k - BK + 1 >= 0; k -= BK) {
+                real cp[BK];
+#pragma unroll
+                for (int q = 0; q < BK; ++q) cp[q] = tc[(k - q) * ny + ky] * o;
+#pragma unroll
+                for (int q = 0; q < BK; ++q) { x = col[2 * (k - q) * nyp] - cp[q] * x; col[2 * (k - q) * nyp] = x; }
+            }
+            for (; k >= 0; --k) { const real cp = tc[k * ny + ky] * o; x = col[2 * k * nyp] - cp * x; col[2 * k * nyp] = x; }
+            carry[t] = x;
+        }
+        pencil_barrier();
+        const real2 *Q = pencil_lines(P, P == S ? D : S, kc, ny, pl.ny1, pl.ny2, nyp, twy, +1);
+        chunk_store(io + (size_t)k0 * ny, Q, kc * ny, ny, nyp);
+        if (c > 0) pencil_barrier();                              // S is overwritten by the chunk below
+    }
+}
+
 // Kernel C: RY rows of one level plus the row below them (the halo d(phi)/dy needs): Hermitian halves rebuilt from m = 0 .. nx/2,
 // two real rows per complex line, inverse x transform, phi = result / (nx ny); then u -= dts d(phi)/dx, v -= dts d(phi)/dy with the
 // operand order of k3_correct, and phi of the RY rows to the phi buffer (k3_correct_w reads it).  A masked env is left alone.

@@ -272,6 +272,7 @@ void rbc_default_config(rbc_config *c)
     c->batch = 1; c->device = 0; c->write_state = 1;
     c->precision = RBC_PRECISION_F64;
     c->reference_clock = RBC_CLOCK_DOCUMENTED;
+    c->projection = RBC_PROJECTION_AUTO;
 }
 
 int rbc_create(const rbc_config *cfg, rbc_handle **out)
@@ -284,6 +285,8 @@ int rbc_create(const rbc_config *cfg, rbc_handle **out)
     if (!rbc_has_precision(cfg->precision)) return fail(RBC_ERR_INVALID, "precision must be RBC_PRECISION_F64 or RBC_PRECISION_F32");
     if (cfg->reference_clock != RBC_CLOCK_DOCUMENTED && cfg->reference_clock != RBC_CLOCK_RECORDED)
         return fail(RBC_ERR_INVALID, "reference_clock must be RBC_CLOCK_DOCUMENTED or RBC_CLOCK_RECORDED");
+    if (cfg->dim == 3 && (cfg->projection < RBC_PROJECTION_AUTO || cfg->projection > RBC_PROJECTION_CHUNKED))
+        return fail(RBC_ERR_INVALID, "projection must be RBC_PROJECTION_AUTO, RBC_PROJECTION_PENCIL or RBC_PROJECTION_CHUNKED");
     if (cfg->heaters < 1 || cfg->heaters > rbc::MAX_HEATERS) return fail(RBC_ERR_INVALID, "heaters out of range");
     if (!(cfg->ra > 0) || !(cfg->pr > 0) || !(cfg->dt_solver > 0) || !(cfg->dt_control > 0))
         return fail(RBC_ERR_INVALID, "ra, pr, dt_solver, dt_control must be positive");
@@ -1243,6 +1246,13 @@ int rbc_debug_tendency_path(rbc_handle *h, int *path)
 {
     if (!h || !path) return fail(RBC_ERR_INVALID, "null argument");
     *path = h->s3 ? RBC_S3(h, tendency_path3d, h) : -1;
+    return RBC_OK;
+}
+
+int rbc_debug_projection_path(rbc_handle *h, int *path)
+{
+    if (!h || !path) return fail(RBC_ERR_INVALID, "null argument");
+    *path = h->s3 ? RBC_S3(h, projection_path3d, h) : -1;
     return RBC_OK;
 }
 

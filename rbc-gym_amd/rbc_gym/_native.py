@@ -16,7 +16,7 @@ ROOT = os.path.dirname(_PKG)                      # rbc-gym_amd/
 LIB_PATH = os.path.join(ROOT, "lib", "librbc_hip.so")
 
 RBC_OK, RBC_ERR_INVALID, RBC_ERR_DEVICE, RBC_ERR_NAN, RBC_ERR_NOT_INITIALIZED = range(5)
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 
 class RbcConfig(C.Structure):
@@ -30,7 +30,7 @@ class RbcConfig(C.Structure):
                 ("random_kick", C.c_double),
                 ("obs_nx", C.c_int32), ("obs_nz", C.c_int32),
                 ("batch", C.c_int32), ("device", C.c_int32), ("write_state", C.c_int32), ("precision", C.c_int32),
-                ("reference_clock", C.c_int32)]
+                ("reference_clock", C.c_int32), ("projection", C.c_int32)]
 
 class RbcRender3Params(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("view_from", C.c_double * 3), ("clim", C.c_double * 2),
@@ -42,6 +42,19 @@ PRECISIONS = {"f64": 0, "f32": 1}
 # sources say (rbc_sim2D_api.jl:84-85); "recorded" = what its recorded flowstats series show: the first env-step after a reset
 # carries all its solver steps, every later one of them one less
 CLOCKS = {"documented": 0, "recorded": 1}
+
+
+# rbc_config.projection (include/rbc_hip.h), dim = 3: "auto" = slab kernels or the row / pencil projection by the grid; "pencil" forces
+# the latter; "chunked" = the pencil projection with the (y, z) plane walked in chunks of levels: grids beyond the one-plane bound
+PROJECTIONS = {"auto": 0, "pencil": 1, "chunked": 2}
+
+
+def projection_code(name):
+    if name in PROJECTIONS:
+        return PROJECTIONS[name]
+    if isinstance(name, (int, np.integer)) and not isinstance(name, bool):
+        return int(name)                                     # the library validates the number (tests hand it a wrong one)
+    raise ValueError(f"projection must be one of {sorted(PROJECTIONS)}, got {name!r}")
 
 
 def clock_code(name):
@@ -97,6 +110,7 @@ SYMBOLS = {
     "rbc_debug_stamps": (C.c_int, [_vp, _u64p]),
     "rbc_debug_launch_plan": (C.c_int, [_vp, _i32p]),
     "rbc_debug_tendency_path": (C.c_int, [_vp, _i32p]),
+    "rbc_debug_projection_path": (C.c_int, [_vp, _i32p]),
     "rbc_reset_from_arrays3": (C.c_int, [_vp, _u8p, _dp, _dp, _dp, _dp]),
     "rbc_get_fields3": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     "rbc_debug_tendencies3": (C.c_int, [_vp, _fp, _dp, _dp, _dp, _dp]),
@@ -536,11 +550,12 @@ class NativeSim3D(_FlowStats, _Spectra):
 
     def __init__(self, batch=1, device=0, shape=(16, 32, 32), domain=(2.0, 4 * np.pi, 4 * np.pi), ra=2500.0, pr=0.7,
                  t_diff=(1.0, 2.0), heaters=8, heater_limit=0.9, dt_control=0.125, dt_solver=0.01, random_kick=None, precision=0,
-                 reference_clock="documented"):
+                 reference_clock="documented", projection="auto"):
         self.lib = load_library()
         cfg = default_config()
         cfg.precision = int(PRECISIONS.get(precision, precision))
         cfg.reference_clock = clock_code(reference_clock)
+        cfg.projection = projection_code(projection)
         nz, ny, nx = shape
         lz, ly, lx = domain
         cfg.dim, cfg.nx, cfg.ny, cfg.nz = 3, int(nx), int(ny), int(nz)
@@ -696,6 +711,13 @@ class NativeSim3D(_FlowStats, _Spectra):
         -- include/rbc_hip.h rbc_debug_tendency_path"""
         p = np.zeros(1, np.int32)
         self._check(self.lib.rbc_debug_tendency_path(self.h, _ptr(p, _i32p)))
+        return int(p[0])
+
+    def projection_path(self):
+        """which pressure projection a stage launches: 0 slab kernels, 1 row / pencil with the one-plane y-z solve, 2 with the chunked
+        y-z solve -- include/rbc_hip.h rbc_debug_projection_path"""
+        p = np.zeros(1, np.int32)
+        self._check(self.lib.rbc_debug_projection_path(self.h, _ptr(p, _i32p)))
         return int(p[0])
 
     def synchronize(self):

@@ -50,6 +50,7 @@ class RayleighBenardConvection3DEnv(NativeEnvBase):
         reference_clock: str = "documented",   # "recorded": the solver-step count of the reference's recorded series
         render_size: tuple = (800, 608),       # (width, height) of a frame: the reference's window_size (rbc3D.py:297)
         view_from: tuple = (1, 1, 1),          # direction from the scene towards the camera; (1, 1, 1) is PyVista's isometric view
+        projection: str = "auto",              # "pencil" | "chunked": see _native.PROJECTIONS ("chunked" serves 128 x 128 x 64 and beyond)
     ) -> None:
         super().__init__()
         self.render_size, self.view_from = tuple(int(n) for n in render_size), tuple(float(x) for x in view_from)
@@ -67,7 +68,8 @@ class RayleighBenardConvection3DEnv(NativeEnvBase):
         sim = _native.NativeSim3D(batch=1, device=device, shape=tuple(state_shape), domain=tuple(domain), ra=float(rayleigh_number),
                                   pr=float(prandtl_number), t_diff=tuple(temperature_difference), heaters=heater_segments,
                                   heater_limit=heater_limit, dt_control=heater_duration, dt_solver=dt_solver, precision=precision,
-                                  reference_clock=reference_clock)
+                                  reference_clock=reference_clock, projection=projection)
+        self.projection = projection
         self._setup(sim, episode_length, checkpoint, render_mode, env_logger(__name__, log_dir, env_id))
 
     def _checked_action(self, action):

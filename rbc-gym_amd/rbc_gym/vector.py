@@ -246,7 +246,7 @@ class RayleighBenardConvection3DVectorEnv(_BatchedEnv):
                  state_shape=(16, 32, 32), temperature_difference=(1, 2), heater_segments=8, heater_limit=0.9,
                  heater_duration=0.125, episode_length=300, dt_solver=0.01, use_gpu=True, checkpoint=None, checkpoint_idx=None,
                  render_mode=None, device=0, devices=None, precision="f64", obs_buffers=None, reference_clock="documented",
-                 render_size=(800, 608), view_from=(1, 1, 1), **_ignored):
+                 render_size=(800, 608), view_from=(1, 1, 1), projection="auto", **_ignored):
         # obs_buffers: None = every reset / step returns a new observation array as far as the caller can tell (the reference's
         # behaviour; large ones come from _native.PinnedPool: a page-locked array is reused only once the caller has dropped it),
         # "fresh" = always np.empty (the A/B partner), "pinned" = the observations rotate over three page-locked buffers
@@ -273,7 +273,8 @@ class RayleighBenardConvection3DVectorEnv(_BatchedEnv):
             return _native.NativeSim3D(batch=count, device=dev, shape=tuple(state_shape), domain=tuple(domain), ra=ra0,
                                        pr=float(prandtl_number), t_diff=tuple(temperature_difference), heaters=heater_segments,
                                        heater_limit=heater_limit, dt_control=heater_duration, dt_solver=dt_solver, precision=precision,
-                                       reference_clock=reference_clock)
+                                       reference_clock=reference_clock, projection=projection)
+        self.projection = projection                                 # "pencil" | "chunked": see _native.PROJECTIONS; every shard runs the same
         self.devices = None if devices is None else [int(d) for d in devices]
         self.sim = make(self.num_envs, device) if self.devices is None else ShardedSim(make, self.num_envs, self.devices)
         if np.ndim(rayleigh_number) > 0:
